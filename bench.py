@@ -5,7 +5,7 @@ metric : fp64 forward+adjoint ODE solves/sec at rtol=1e-8 (Lotka-Volterra, confi
          rtol=atol=1e-8 for the forward, backward and quadrature problems, grads = ones)
 step   : one forward (sa_solve_forward_batch) + one adjoint (sa_solve_backward_batch) pass over the
          whole batch, inputs and outputs resident in HBM (torch tensors, SA_MEM_DEVICE).
-N > 1  : `python bench.py --gpus N` starts N ranks itself (re-exec under torch.distributed.run on
+N > 1  : `python bench.py --gpus N` starts N ranks itself (a child torch.distributed.run on
          127.0.0.1) unless it already runs under one (WORLD_SIZE set, as the driver launches it);
          one process per GPU, RCCL only for the barrier, the max-reduce of the elapsed time and the
          sum of the failed-instance counts; the batch shards by instance through
@@ -177,8 +177,17 @@ class GpuEngine:
                     head_grads=self.grad_out[:16, :max(self.p, 1)].cpu().numpy(),
                     head_lamda=self.lamda_out[:16].cpu().numpy())
 
+    def outputs(self):
+        """The result arrays of the last step, as a caller of this path receives them (host copies, batch first)."""
+        self.sync()
+        return {k: getattr(self, k).cpu().numpy() for k in OUTPUT_NAMES}
+
     def close(self):
         self.eng.close()
+
+
+#: the arrays one step hands back (forward: y_out, st_f, stats_f; backward: grad_out, lamda_out, st_b, stats_b)
+OUTPUT_NAMES = ("y_out", "st_f", "stats_f", "grad_out", "lamda_out", "st_b", "stats_b")
 
 
 class MultiDeviceEngine:
@@ -233,10 +242,33 @@ class MultiDeviceEngine:
                 out[key] = rs[0][key]
         return out
 
+    def outputs(self):
+        """The global batch's results: engine k holds rows k*B/N .. (k+1)*B/N - 1."""
+        per = [e.outputs() for e in self.engines]
+        return {k: np.concatenate([o[k] for o in per]) for k in per[0]}
+
     def close(self):
         for e in self.engines:
             e.close()
         self.pool.shutdown()
+
+
+DUMP_BYTES = 64 * 10**6              # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outputs, out_dir, seed=0):
+    """--dump-outputs: every array of `outputs` (batch first) as <out_dir>/<name>.npy in float64 (status codes and
+    counters convert exactly), plus instance.npy, the batch rows written.  Above DUMP_BYTES in all, every array keeps
+    the same seeded sample of rows (ascending), so two builds run with the same arguments compare row for row."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in outputs.items()}
+    B = len(next(iter(arrays.values())))
+    row_bytes = 8 + sum(a[0].nbytes for a in arrays.values())
+    keep = min(B, (DUMP_BYTES - 256 * (len(arrays) + 1)) // row_bytes)       # (256: room for each .npy header)
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(seed).choice(B, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "instance.npy"), rows.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a[rows]))
 
 
 def run_single_process(args, *, make_engine=None):
@@ -270,6 +302,8 @@ def run_single_process(args, *, make_engine=None):
         bwd_ms.append(b)
     eng.sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(eng.outputs(), args.dump_outputs)
     res = eng.results()
     out = summarise(name, prob, w, B, world, args, elapsed, fwd_ms, bwd_ms, res, res["failed"])
     out["config"]["parallelism"] = "instance-sharded x%d, one process, one host thread per device (devices %s)" \
@@ -346,6 +380,8 @@ def run_rank(args, *, backend="nccl", make_engine=None):
         dist.barrier()
     elapsed = all_reduce(own, "MAX")
     fastest = all_reduce(own, "MIN")
+    if args.dump_outputs:
+        dump_outputs(eng.outputs(), args.dump_outputs)
     res = eng.results()
     failed = int(all_reduce(float(res["failed"]), "SUM"))
     out = None
@@ -705,6 +741,7 @@ def extra_configs(args):
             # two untimed steps: the first call on a handle sizes the trajectory arena (and may re-integrate), the
             # second allocates its final size; from the third on the allocation is stable
             sub.workload, sub.batch, sub.steps, sub.warmup, sub.gpus = name, 0, 5, 2, 1
+            sub.dump_outputs = None                   # (the dump is the headline workload's)
             r = run_rank(sub)
             row = {"workload": w["label"], "batch": w["batch"], "solves_per_s": r["value"],
                    "ms_per_step": r["ms_per_step"], "forward_kernel_ms": r["roofline"]["forward_kernel_ms"],
@@ -744,22 +781,29 @@ def parse_args(argv=None):
                                                    "(default 0..N-1; an ordinal may repeat: two engines on one GPU)")
     ap.add_argument("--force-dist", action="store_true",
                     help="form the process group (nccl = RCCL), barrier and device all-reduce even with one rank")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result arrays as DIR/<name>.npy (float64, "
+                         "at most 64 MB in all: a seeded sample of the batch's rows beyond that)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus > 1 and not args.single_process:
+        ap.error("--dump-outputs needs the whole batch in one process (--gpus 1, or --single-process)")
+    return args
 
 
 def launch_ranks(args, argv):
-    """`python bench.py --gpus N` outside torchrun: become `python -m torch.distributed.run ... bench.py ...`."""
+    """`python bench.py --gpus N` outside torchrun: run `python -m torch.distributed.run ... bench.py ...` as a fresh
+    child and exit with its status.  This process never opens a GPU (every rank checks the visible device count)."""
     import socket
-    import torch
-    if torch.cuda.device_count() < args.gpus:
-        raise SystemExit("bench.py: --gpus %d but only %d GPU(s) visible" % (args.gpus, torch.cuda.device_count()))
+    import subprocess
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def main(argv=None):
