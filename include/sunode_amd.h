@@ -45,6 +45,7 @@ extern "C" {
 #define SA_ERR_HIP (-1001)        /* a HIP runtime call failed */
 #define SA_ERR_ARG (-1002)        /* invalid argument / call sequence */
 #define SA_ERR_MODULE (-1003)     /* code object missing, wrong arch or ABI mismatch */
+#define SA_ERR_INTERNAL (-1004)   /* the library contradicts itself (differential guard: its sample is not the batch's) */
 
 /* per-instance status beyond the CVODES codes.  From sa_solve_forward_batch: the instance would store more than
    sa_options.traj_capacity points -- the integration stops there (bounded work, whatever the inputs) and y_out is
@@ -200,6 +201,38 @@ int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, const double *
                                 const double *tvals, int32_t n_t, const double *grads, int64_t grads_stride,
                                 double *grad_out, double *lamda_out, double *lamda_all_out,
                                 double *quad_all_out, int32_t *status, int64_t *stats);
+
+/* Per-instance start times and output grids (the same semantics per instance as the entry points above, called on
+   that instance alone with its own times).  t0 [B] (t0_stride = 1) or [1] (t0_stride = 0); the same for tend;
+   tvals [B][n_t] (tvals_stride = n_t) or [n_t] (tvals_stride = 0): every instance has n_t output times.  The time
+   arrays live where `mem` says, like every other array of the call.  The backward pass reads the initial time of
+   each instance from the preceding forward call (sa_solve_forward_batch or sa_solve_forward_batch_times).  A row
+   that a shared-grid call would refuse (e.g. decreasing times) fails its instance alone, with the status that call
+   returns; the other instances are unaffected.  Outputs and counters are those of the instance solved alone, except
+   stats slot 15 of the backward pass (iterations of the whole wavefront: it depends on the instances sharing it).
+   Synchronisation: a call that mixes per-instance and shared times spreads each shared one over the batch through a
+   host buffer and synchronises the handle's stream once per such time (also for the initial times of a backward call
+   whose forward call had one shared t0), and a device-memory time with stride 0 is read back to the host first (one
+   more synchronisation); a call whose time arguments are all [B] arrays (stride 1) only enqueues, like the plain
+   entry points. */
+int sa_solve_batch_times(sa_solver *s, int mem, int32_t B, const double *y0, const double *ps, const double *pr,
+                         int32_t rem_stride, const double *t0, int32_t t0_stride, const double *tvals,
+                         int64_t tvals_stride, int32_t n_t, double *y_out, int32_t *status, int64_t *stats);
+int sa_solve_sens_batch_times(sa_solver *s, int mem, int ism, const double *scaling, int32_t B, const double *y0,
+                              const double *params_sub, const double *params_rem, int32_t rem_stride,
+                              const double *sens0, const double *t0, int32_t t0_stride, const double *tvals,
+                              int64_t tvals_stride, int32_t n_t, double *y_out, double *sens_out, int32_t *status,
+                              int64_t *stats);
+int sa_solve_forward_batch_times(sa_solver *s, int mem, int32_t B, const double *y0, const double *ps,
+                                 const double *pr, int32_t rem_stride, const double *t0, int32_t t0_stride,
+                                 const double *tvals, int64_t tvals_stride, int32_t n_t, double *y_out,
+                                 int32_t *status, int64_t *stats);
+int sa_solve_backward_batch_times(sa_solver *s, int mem, int32_t B, const double *params_sub,
+                                  const double *params_rem, int32_t rem_stride, const double *t0, int32_t t0_stride,
+                                  const double *tend, int32_t tend_stride, const double *tvals, int64_t tvals_stride,
+                                  int32_t n_t, const double *grads, int64_t grads_stride, double *grad_out,
+                                  double *lamda_out, double *lamda_all_out, double *quad_all_out, int32_t *status,
+                                  int64_t *stats);
 
 /* Evaluate the generated callbacks on the device (what make_sundials_rhs / _jac_dense /
    _adjoint_rhs / _adjoint_quad_rhs / _adjoint_jac_dense compute, problem.py:156-383).

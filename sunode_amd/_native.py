@@ -524,6 +524,13 @@ def load_library() -> ctypes.CDLL:
                                       i32, _dp, _dp, _dp, _dp]
     L.sa_solve_backward_batch_all.argtypes = [vp, ctypes.c_int, i32, _dp, _dp, i32, dbl, dbl, _dp, i32, _dp, i64,
                                               _dp, _dp, _dp, _dp, _dp, _dp]
+    fwd_t = [vp, ctypes.c_int, i32, _dp, _dp, _dp, i32, _dp, i32, _dp, i64, i32, _dp, _dp, _dp]
+    L.sa_solve_batch_times.argtypes = fwd_t
+    L.sa_solve_forward_batch_times.argtypes = fwd_t
+    L.sa_solve_sens_batch_times.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, i32, _dp, _dp, _dp, i32, _dp, _dp,
+                                            i32, _dp, i64, i32, _dp, _dp, _dp, _dp]
+    L.sa_solve_backward_batch_times.argtypes = [vp, ctypes.c_int, i32, _dp, _dp, i32, _dp, i32, _dp, i32, _dp, i64,
+                                                i32, _dp, i64, _dp, _dp, _dp, _dp, _dp, _dp]
     L.sa_eval_callbacks.argtypes = [vp, ctypes.c_int, i32] + [_dp] * 11
     L.sa_math_probe.argtypes = [vp, i32] + [_dp] * 5
     L.sa_arena_info.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32)]
@@ -538,7 +545,8 @@ def load_library() -> ctypes.CDLL:
                                  ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_char_p)]
     for name in ("sa_solver_attach_guard", "sa_guard_state", "sa_solver_create", "sa_solver_set_options", "sa_solver_sizes", "sa_solve_batch", "sa_solve_sens_batch",
                  "sa_solve_forward_batch", "sa_solve_backward_batch", "sa_solve_backward_batch_all",
-                 "sa_eval_callbacks", "sa_math_probe", "sa_last_kernel_ms", "sa_set_stream", "sa_synchronize",
+                 "sa_solve_batch_times", "sa_solve_forward_batch_times", "sa_solve_sens_batch_times",
+                 "sa_solve_backward_batch_times", "sa_eval_callbacks", "sa_math_probe", "sa_last_kernel_ms", "sa_set_stream", "sa_synchronize",
                  "sa_arena_info", "sa_device_count", "sa_device_memory"):
         getattr(L, name).restype = ctypes.c_int
     _LIB = L
@@ -548,7 +556,9 @@ def load_library() -> ctypes.CDLL:
 EXPORTED_SYMBOLS = ["sa_abi_version", "sa_last_error", "sa_solver_create", "sa_solver_destroy",
                     "sa_solver_set_options", "sa_solver_sizes", "sa_solve_batch", "sa_solve_sens_batch",
                     "sa_solve_forward_batch",
-                    "sa_solve_backward_batch", "sa_solve_backward_batch_all", "sa_eval_callbacks", "sa_math_probe",
+                    "sa_solve_backward_batch", "sa_solve_backward_batch_all",
+                    "sa_solve_batch_times", "sa_solve_forward_batch_times", "sa_solve_sens_batch_times",
+                    "sa_solve_backward_batch_times", "sa_eval_callbacks", "sa_math_probe",
                     "sa_last_kernel_ms", "sa_arena_info",
                     "sa_set_stream", "sa_synchronize", "sa_device_count", "sa_device_memory",
                     "sa_solver_attach_guard", "sa_guard_state"]
@@ -757,33 +767,74 @@ class NativeSolver:
         return self.synchronize
 
     # -- raw entry points (addresses or numpy arrays; shapes are the caller's responsibility) --
-    def solve(self, mem, B, y0, ps, pr, rem_stride, t0, tvals, n_t, y_out, status, stats, adjoint=False):
-        done = self._torch_guard(y0, ps, pr, tvals, y_out, status, stats)
-        fn = self.L.sa_solve_forward_batch if adjoint else self.L.sa_solve_batch
-        self._check(fn(self._h, mem, B, _addr(y0), _addr(ps), _addr(pr), rem_stride, float(t0), _addr(tvals),
-                       n_t, _addr(y_out), _addr(status), _addr(stats)))
+    # Time arguments: a Python number / 0-d array t0 (tend) and a 1-d grid go through the shared-grid entry points as
+    # before; ``t0_stride`` / ``tend_stride`` / ``tvals_stride`` not None select the per-instance entry points
+    # (include/sunode_amd.h sa_*_batch_times) with t0 (tend, tvals) an array or device pointer and that stride.
+    @staticmethod
+    def _time_arg(x, stride, mem):
+        """(buffer, stride) of one time argument of a per-instance entry point: a number becomes a one-element host
+        array (stride 0) -- the caller keeps the buffer alive across the call."""
+        if stride is None:
+            if mem != SA_MEM_HOST:
+                raise ValueError("a shared time of a device-memory call must be a one-element device array (stride 0)")
+            return np.asarray([x], dtype=np.float64), 0
+        if isinstance(x, (np.ndarray, int, np.integer)) or hasattr(x, "data_ptr"):
+            return x, int(stride)
+        raise TypeError("a per-instance time argument must be an array, a tensor or a device pointer")
+
+    def solve(self, mem, B, y0, ps, pr, rem_stride, t0, tvals, n_t, y_out, status, stats, adjoint=False,
+              t0_stride=None, tvals_stride=None):
+        done = self._torch_guard(y0, ps, pr, tvals, y_out, status, stats, t0)
+        if t0_stride is None and tvals_stride is None:
+            fn = self.L.sa_solve_forward_batch if adjoint else self.L.sa_solve_batch
+            rc = fn(self._h, mem, B, _addr(y0), _addr(ps), _addr(pr), rem_stride, float(t0), _addr(tvals),
+                    n_t, _addr(y_out), _addr(status), _addr(stats))
+        else:
+            fn = self.L.sa_solve_forward_batch_times if adjoint else self.L.sa_solve_batch_times
+            t0b, t0s = self._time_arg(t0, t0_stride, mem)
+            rc = fn(self._h, mem, B, _addr(y0), _addr(ps), _addr(pr), rem_stride, _addr(t0b), t0s,
+                    _addr(tvals), int(tvals_stride or 0), n_t, _addr(y_out), _addr(status), _addr(stats))
+        self._check(rc)
         if done:
             done()
         if self._guard_open:
             self._guard_poll()
 
     def solve_backward(self, mem, B, ps, pr, rem_stride, t0, tend, tvals, n_t, grads, grads_stride, grad_out,
-                       lamda_out, status, stats, lamda_all=None, quad_all=None):
-        done = self._torch_guard(ps, pr, tvals, grads, grad_out, lamda_out, status, stats)
-        self._check(self.L.sa_solve_backward_batch_all(
-            self._h, mem, B, _addr(ps), _addr(pr), rem_stride, float(t0), float(tend), _addr(tvals), n_t,
-            _addr(grads), int(grads_stride), _addr(grad_out), _addr(lamda_out), _addr(lamda_all), _addr(quad_all),
-            _addr(status), _addr(stats)))
+                       lamda_out, status, stats, lamda_all=None, quad_all=None, t0_stride=None, tend_stride=None,
+                       tvals_stride=None):
+        done = self._torch_guard(ps, pr, tvals, grads, grad_out, lamda_out, status, stats, t0, tend)
+        if t0_stride is None and tend_stride is None and tvals_stride is None:
+            rc = self.L.sa_solve_backward_batch_all(
+                self._h, mem, B, _addr(ps), _addr(pr), rem_stride, float(t0), float(tend), _addr(tvals), n_t,
+                _addr(grads), int(grads_stride), _addr(grad_out), _addr(lamda_out), _addr(lamda_all), _addr(quad_all),
+                _addr(status), _addr(stats))
+        else:
+            t0b, t0s = self._time_arg(t0, t0_stride, mem)
+            teb, tes = self._time_arg(tend, tend_stride, mem)
+            rc = self.L.sa_solve_backward_batch_times(
+                self._h, mem, B, _addr(ps), _addr(pr), rem_stride, _addr(t0b), t0s, _addr(teb), tes,
+                _addr(tvals), int(tvals_stride or 0), n_t, _addr(grads), int(grads_stride),
+                _addr(grad_out), _addr(lamda_out), _addr(lamda_all), _addr(quad_all), _addr(status), _addr(stats))
+        self._check(rc)
         if done:
             done()
         if self._guard_open:
             self._guard_poll()
 
     def solve_sens(self, mem, ism, scaling, B, y0, ps, pr, rem_stride, sens0, t0, tvals, n_t, y_out, sens_out,
-                   status, stats):
-        self._check(self.L.sa_solve_sens_batch(self._h, mem, int(ism), _addr(scaling), B, _addr(y0), _addr(ps),
-                                               _addr(pr), rem_stride, _addr(sens0), float(t0), _addr(tvals), n_t,
-                                               _addr(y_out), _addr(sens_out), _addr(status), _addr(stats)))
+                   status, stats, t0_stride=None, tvals_stride=None):
+        if t0_stride is None and tvals_stride is None:
+            rc = self.L.sa_solve_sens_batch(self._h, mem, int(ism), _addr(scaling), B, _addr(y0), _addr(ps),
+                                            _addr(pr), rem_stride, _addr(sens0), float(t0), _addr(tvals), n_t,
+                                            _addr(y_out), _addr(sens_out), _addr(status), _addr(stats))
+        else:
+            t0b, t0s = self._time_arg(t0, t0_stride, mem)
+            rc = self.L.sa_solve_sens_batch_times(self._h, mem, int(ism), _addr(scaling), B, _addr(y0), _addr(ps),
+                                                  _addr(pr), rem_stride, _addr(sens0), _addr(t0b), t0s,
+                                                  _addr(tvals), int(tvals_stride or 0), n_t,
+                                                  _addr(y_out), _addr(sens_out), _addr(status), _addr(stats))
+        self._check(rc)
         if self._guard_open:
             self._guard_poll()
 

@@ -936,7 +936,10 @@ DEV void store_point(double *r, int order, double t, const double (&y)[NSD])
 #else
 #define SA_FWD_ATTR
 #endif
-extern "C" __global__ void __launch_bounds__(64) SA_FWD_ATTR sa_k_forward(sa_fwd_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_forward(const sa_fwd_args &a)
 {
     const int inst = blockIdx.x * 64 + threadIdx.x;
     if (inst >= a.B) return;
@@ -962,7 +965,7 @@ extern "C" __global__ void __launch_bounds__(64) SA_FWD_ATTR sa_k_forward(sa_fwd
 
     double y0[NSD];
     SFOR(i, 0, NS) y0[i] = a.y0[(int64_t)inst * NS + i]; SEND
-    { double q0_[NQD]; SFOR(i, 0, NQD) q0_[i] = 0.0; SEND cv_reinit(m, a.t0, y0, q0_); }
+    { double q0_[NQD]; SFOR(i, 0, NQD) q0_[i] = 0.0; SEND cv_reinit(m, SA_T0(a, inst), y0, q0_); }
 
     /* store: CVodeF semantics (every step is a data point, no mxstep budget); wr: the points are written to the
        arena (SA_MODE_ADJ_COUNT runs the identical pass and only counts them, see sunode_amd.cpp) */
@@ -974,15 +977,15 @@ extern "C" __global__ void __launch_bounds__(64) SA_FWD_ATTR sa_k_forward(sa_fwd
     SFOR(j, 0, (QMAX) + 1) { hT[j] = 0.0; SFOR(i, 0, NS) hY[j][i] = 0.0; SEND } SEND
 
     int status = CV_SUCCESS, k = 0, np = 0, nstloc = 0, retries = 0, total_retries = 0, attempts = 0;
-    while (k < a.n_t && a.tvals[k] == a.t0) {       /* solver.py:505,707 (row k; the reference writes row 0) */
+    while (k < a.n_t && SA_TV(a, inst, k) == SA_T0(a, inst)) {       /* solver.py:505,707 (row k; the reference writes row 0) */
         SFOR(i, 0, NS) yo[(int64_t)k * NS + i] = y0[i]; SEND
         k++;
     }
     bool done = (k >= a.n_t);
     StepCtl c;
-    c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.convfail = 0; c.saved_t = a.t0;
+    c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.convfail = 0; c.saved_t = SA_T0(a, inst);
     if (!done) {
-        int flag = cv_first_call(m, a.tvals[k]);
+        int flag = cv_first_call(m, SA_TV(a, inst, k));
         if (flag != CV_SUCCESS) { status = flag; done = true; }
         else if (store) {
             hT[0] = m.tn;
@@ -1034,8 +1037,8 @@ extern "C" __global__ void __launch_bounds__(64) SA_FWD_ATTR sa_k_forward(sa_fwd
                     }
                 }
                 while (!done && k < a.n_t) {
-                    double tout = a.tvals[k];
-                    if (tout == a.t0) {       /* (re-read: y0 is not worth NS register pairs across the whole loop) */
+                    double tout = SA_TV(a, inst, k);
+                    if (tout == SA_T0(a, inst)) {       /* (re-read: y0 is not worth NS register pairs across the whole loop) */
                         SFOR(i, 0, NS) yo[(int64_t)k * NS + i] = a.y0[(int64_t)inst * NS + i]; SEND
                         k++;
                     } else if ((m.tn - tout) * m.h >= 0.0) {
@@ -1073,12 +1076,17 @@ extern "C" __global__ void __launch_bounds__(64) SA_FWD_ATTR sa_k_forward(sa_fwd
 #endif
     SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
 }
+extern "C" __global__ void __launch_bounds__(64) SA_FWD_ATTR sa_k_forward(sa_fwd_args a) { k_forward<false>(a); }
+extern "C" __global__ void __launch_bounds__(64) SA_FWD_ATTR sa_k_forward_t(sa_fwd_args a) { k_forward<true>(a); }
 
 #ifdef SA_SENS
 /* Solver(sens_mode=...).solve (reference solver.py:360-392, 497-531): the forward problem together with its
    NQ sensitivity systems, one instance per thread, everything in registers.  Same control flow as sa_k_forward
    without the trajectory; bit-identical to bdf_mem.hip's sa_k_sens (and to the oracle). */
-extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_sens(const sa_sens_args &a)
 {
     const int inst = blockIdx.x * 64 + threadIdx.x;
     if (inst >= a.B) return;
@@ -1104,13 +1112,13 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     double y0[NSD], s0[NQD][NSD];
     SFOR(i, 0, NS) y0[i] = a.y0[(int64_t)inst * NS + i]; SEND
     SFOR_S(is, i) s0[is][i] = a.sens0[((int64_t)inst * NQ + is) * NS + i]; SEND_S
-    { double q0_[NQD]; SFOR(i, 0, NQD) q0_[i] = 0.0; SEND cv_reinit(m, a.t0, y0, q0_); }
+    { double q0_[NQD]; SFOR(i, 0, NQD) q0_[i] = 0.0; SEND cv_reinit(m, SA_T0(a, inst), y0, q0_); }
     SFOR(v, 0, SV_COUNT) { SFOR_S(is, i) m.sv[v][is][i] = (v == SV_ZN0) ? s0[is][i] : 0.0; SEND_S } SEND
 
     double *yo = a.y_out + (int64_t)inst * a.n_t * NS;
     double *so = a.sens_out + (int64_t)inst * a.n_t * NQ * NS;
     int status = CV_SUCCESS, k = 0, nstloc = 0, retries = 0, total_retries = 0, attempts = 0;
-    while (k < a.n_t && a.tvals[k] == a.t0) {
+    while (k < a.n_t && SA_TV(a, inst, k) == SA_T0(a, inst)) {
         SFOR(i, 0, NS) yo[(int64_t)k * NS + i] = y0[i]; SEND
         SFOR_S(is, i) so[((int64_t)k * NQ + is) * NS + i] = s0[is][i]; SEND_S
         k++;
@@ -1118,9 +1126,9 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     bool done = (k >= a.n_t);
     StepCtl c;
     c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.ncfS = c.nefS = 0; c.convfail = 0;
-    c.saved_t = a.t0;
+    c.saved_t = SA_T0(a, inst);
     if (!done) {
-        int flag = cv_first_call(m, a.tvals[k]);
+        int flag = cv_first_call(m, SA_TV(a, inst, k));
         if (flag != CV_SUCCESS) { status = flag; done = true; }
     }
     while (!done) {
@@ -1141,8 +1149,8 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
             else if (r == 1) {
                 nstloc++;
                 while (!done && k < a.n_t) {
-                    double tout = a.tvals[k];
-                    if (tout == a.t0) {
+                    double tout = SA_TV(a, inst, k);
+                    if (tout == SA_T0(a, inst)) {
                         SFOR(i, 0, NS) yo[(int64_t)k * NS + i] = y0[i]; SEND
                         SFOR_S(is, i) so[((int64_t)k * NQ + is) * NS + i] = s0[is][i]; SEND_S
                         k++;
@@ -1183,6 +1191,8 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     st[ST_RETRIES] = total_retries; st[ST_ATTEMPTS] = attempts;
     SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
 }
+extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a) { k_sens<false>(a); }
+extern "C" __global__ void __launch_bounds__(64) sa_k_sens_t(sa_sens_args a) { k_sens<true>(a); }
 #endif
 
 /* ------------------------------------------------------------------------------------ */
@@ -1193,7 +1203,10 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
 #else
 #define SA_BWD_ATTR
 #endif
-extern "C" __global__ void __launch_bounds__(64) SA_BWD_ATTR sa_k_backward(sa_bwd_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_backward(const sa_bwd_args &a)
 {
 #if !SA_TAB_REGS
     __shared__ double ltab[TTAB * 64];        /* per-lane copy of the current divided-difference table */
@@ -1211,11 +1224,11 @@ extern "C" __global__ void __launch_bounds__(64) SA_BWD_ATTR sa_k_backward(sa_bw
     m.rtol = a.rtolB;
     SFOR(i, 0, NS) m.atol[i] = a.atolB; SEND
     m.rtolQ = a.rtolQB; m.atolQ = a.atolQB;
-    m.tstop = a.tinitial;
+    m.tstop = SA_TINIT(a, inst);
     m.traj = a.traj + (int64_t)inst * a.traj_istride * TREC;
     m.trow = a.traj_stride * TREC;
     m.np = np;
-    m.tfinal = (status == CV_SUCCESS) ? m.traj[(int64_t)(np - 1) * m.trow + TREC_T] : a.tinitial;
+    m.tfinal = (status == CV_SUCCESS) ? m.traj[(int64_t)(np - 1) * m.trow + TREC_T] : SA_TINIT(a, inst);
     m.cur_idx = 0; m.tlo2 = 0.0;
 #if SA_SEARCH_CACHE
     m.thi2 = 0.0; m.thi2_idx = -1;
@@ -1243,7 +1256,7 @@ extern "C" __global__ void __launch_bounds__(64) SA_BWD_ATTR sa_k_backward(sa_bw
     const double *g = a.grads + (int64_t)inst * a.grads_stride;
     bool first_call = true;
     int total_retries = 0, attempts = 0, wave_iters = 0;
-    cv_reinit(m, a.t0, lam, quad);
+    cv_reinit(m, SA_T0(a, inst), lam, quad);
 
     /* ts = [t0] + reversed(tvals) + [tend]; interval iv = (ts[iv+1], ts[iv]).  The wavefront walks the intervals
        together: every lane waits for the slowest at each observation, then all restart at once.
@@ -1255,18 +1268,18 @@ extern "C" __global__ void __launch_bounds__(64) SA_BWD_ATTR sa_k_backward(sa_bw
        what follows a restart (order-one steps, a matrix set-up with a fresh Jacobian in nearly every attempt while
        the step size grows) is cheap only while all 64 lanes go through it in the same iterations.) */
     for (int iv = 0; iv <= a.n_t; iv++) {
-        const double t_upper = (iv == 0) ? a.t0 : a.tvals[a.n_t - iv];
-        const double t_lower = (iv == a.n_t) ? a.tend : a.tvals[a.n_t - 1 - iv];
+        const double t_upper = (iv == 0) ? SA_T0(a, inst) : SA_TV(a, inst, a.n_t - iv);
+        const double t_lower = (iv == a.n_t) ? SA_TEND(a, inst) : SA_TV(a, inst, a.n_t - 1 - iv);
         if (t_lower < t_upper) {
             if (status == CV_SUCCESS) {
                 cv_reinit(m, t_upper, lam, quad);          /* CVodeReInitB + CVodeQuadReInitB */
                 if (first_call) {
-                    if ((t_upper - a.tinitial) < 0.0 || (m.tfinal - t_upper) < 0.0) status = CV_BAD_TB0;
+                    if ((t_upper - SA_TINIT(a, inst)) < 0.0 || (m.tfinal - t_upper) < 0.0) status = CV_BAD_TB0;
                     first_call = false;
                 }
-                if (status == CV_SUCCESS && ((t_lower - a.tinitial) < 0.0 || (m.tfinal - t_lower) < 0.0)) {
-                    double tfuzz = 100.0 * UROUND * (fabs(a.tinitial) + fabs(m.tfinal));
-                    if ((t_lower - a.tinitial) < -tfuzz || (m.tfinal - t_lower) < -tfuzz) status = CV_ILL_INPUT;
+                if (status == CV_SUCCESS && ((t_lower - SA_TINIT(a, inst)) < 0.0 || (m.tfinal - t_lower) < 0.0)) {
+                    double tfuzz = 100.0 * UROUND * (fabs(SA_TINIT(a, inst)) + fabs(m.tfinal));
+                    if ((t_lower - SA_TINIT(a, inst)) < -tfuzz || (m.tfinal - t_lower) < -tfuzz) status = CV_ILL_INPUT;
                 }
                 if (status == CV_SUCCESS) {
                     int flag = cv_first_call(m, t_lower);
@@ -1353,6 +1366,8 @@ extern "C" __global__ void __launch_bounds__(64) SA_BWD_ATTR sa_k_backward(sa_bw
 #endif
     SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
 }
+extern "C" __global__ void __launch_bounds__(64) SA_BWD_ATTR sa_k_backward(sa_bwd_args a) { k_backward<false>(a); }
+extern "C" __global__ void __launch_bounds__(64) SA_BWD_ATTR sa_k_backward_t(sa_bwd_args a) { k_backward<true>(a); }
 
 /* ------------------------------------------------------------------------------------ */
 /* callback evaluation (EvalRhs op, codegen parity tests) and arithmetic probes            */

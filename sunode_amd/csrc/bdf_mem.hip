@@ -538,7 +538,10 @@ DEV void init_state(Cm<BWD> &m, double *ws, int64_t ws_stride, int inst, const d
 }
 
 /* ------------------------------------------------------------------------------------ */
-extern "C" __global__ void __launch_bounds__(64) sa_k_forward(sa_fwd_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_forward(const sa_fwd_args &a)
 {
     const int inst = blockIdx.x * 64 + threadIdx.x;
     if (inst >= a.B) return;
@@ -549,7 +552,7 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_forward(sa_fwd_args a)
 
     const Vec y0{const_cast<double *>(a.y0) + (int64_t)inst * NS, 1};
     const Vec q0 = wvec(m, O_QUAD);                       /* (no quadratures in the forward problem: never read) */
-    cv_reinit(m, a.t0, y0, q0);
+    cv_reinit(m, SA_T0(a, inst), y0, q0);
 
     /* store: CVodeF semantics (every step is a data point, no mxstep budget); wr: the points are written to the
        arena (SA_MODE_ADJ_COUNT runs the identical pass and only counts them, see sunode_amd.cpp) */
@@ -562,15 +565,15 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_forward(sa_fwd_args a)
     for (int j = 0; j <= QMAX; j++) for (int i = 0; i < NS; i++) W(m, O_HY, j * NS + i) = 0.0;
 
     int status = CV_SUCCESS, k = 0, np = 0, nstloc = 0, retries = 0, total_retries = 0, attempts = 0;
-    while (k < a.n_t && a.tvals[k] == a.t0) {
+    while (k < a.n_t && SA_TV(a, inst, k) == SA_T0(a, inst)) {
         for (int i = 0; i < NS; i++) yo[(int64_t)k * NS + i] = y0[i];
         k++;
     }
     bool done = (k >= a.n_t);
     StepCtl c;
-    c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.ncfS = c.nefS = 0; c.convfail = 0; c.saved_t = a.t0;
+    c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.ncfS = c.nefS = 0; c.convfail = 0; c.saved_t = SA_T0(a, inst);
     if (!done) {
-        int flag = cv_first_call(m, a.tvals[k]);
+        int flag = cv_first_call(m, SA_TV(a, inst, k));
         if (flag != CV_SUCCESS) { status = flag; done = true; }
         else if (store) {
 #ifdef SA_HERMITE
@@ -617,8 +620,8 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_forward(sa_fwd_args a)
                     }
                 }
                 while (!done && k < a.n_t) {
-                    double tout = a.tvals[k];
-                    if (tout == a.t0) {
+                    double tout = SA_TV(a, inst, k);
+                    if (tout == SA_T0(a, inst)) {
                         for (int i = 0; i < NS; i++) yo[(int64_t)k * NS + i] = y0[i];
                         k++;
                     } else if ((m.tn - tout) * m.h >= 0.0) {
@@ -647,8 +650,13 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_forward(sa_fwd_args a)
     st[ST_NPTS] = np; st[ST_RETRIES] = total_retries; st[ST_ATTEMPTS] = attempts;
     SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
 }
+extern "C" __global__ void __launch_bounds__(64) sa_k_forward(sa_fwd_args a) { k_forward<false>(a); }
+extern "C" __global__ void __launch_bounds__(64) sa_k_forward_t(sa_fwd_args a) { k_forward<true>(a); }
 
-extern "C" __global__ void __launch_bounds__(64) sa_k_backward(sa_bwd_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_backward(const sa_bwd_args &a)
 {
     const int inst = blockIdx.x * 64 + threadIdx.x;
     if (inst >= a.B) return;
@@ -662,11 +670,11 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_backward(sa_bwd_args a)
     init_state(m, a.ws, a.ws_stride, inst, a.ps, a.pr, a.rem_stride);
     m.rtol = a.rtolB; m.atol = Atol{nullptr, a.atolB};
     m.rtolQ = a.rtolQB; m.atolQ = a.atolQB;
-    m.tstop = a.tinitial;
+    m.tstop = SA_TINIT(a, inst);
     m.traj = a.traj + inst;
     m.tS = a.traj_stride;
     m.np = np;
-    m.tfinal = (status == CV_SUCCESS) ? rec(m, np - 1, 2) : a.tinitial;
+    m.tfinal = (status == CV_SUCCESS) ? rec(m, np - 1, 2) : SA_TINIT(a, inst);
     m.newdata = 1;
 
     const Vec lam = wvec(m, O_LAM), quad = wvec(m, O_QUAD), quad_out = wvec(m, O_QOUT);
@@ -675,21 +683,21 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_backward(sa_bwd_args a)
     const double *g = a.grads + (int64_t)inst * a.grads_stride;
     bool first_call = true;
     int total_retries = 0, attempts = 0;
-    cv_reinit(m, a.t0, lam, quad);
+    cv_reinit(m, SA_T0(a, inst), lam, quad);
 
     for (int iv = 0; iv <= a.n_t; iv++) {
-        const double t_upper = (iv == 0) ? a.t0 : a.tvals[a.n_t - iv];
-        const double t_lower = (iv == a.n_t) ? a.tend : a.tvals[a.n_t - 1 - iv];
+        const double t_upper = (iv == 0) ? SA_T0(a, inst) : SA_TV(a, inst, a.n_t - iv);
+        const double t_lower = (iv == a.n_t) ? SA_TEND(a, inst) : SA_TV(a, inst, a.n_t - 1 - iv);
         if (t_lower < t_upper) {
             if (status == CV_SUCCESS) {
                 cv_reinit(m, t_upper, lam, quad);          /* CVodeReInitB + CVodeQuadReInitB */
                 if (first_call) {
-                    if ((t_upper - a.tinitial) < 0.0 || (m.tfinal - t_upper) < 0.0) status = CV_BAD_TB0;
+                    if ((t_upper - SA_TINIT(a, inst)) < 0.0 || (m.tfinal - t_upper) < 0.0) status = CV_BAD_TB0;
                     first_call = false;
                 }
-                if (status == CV_SUCCESS && ((t_lower - a.tinitial) < 0.0 || (m.tfinal - t_lower) < 0.0)) {
-                    double tfuzz = 100.0 * UROUND * (fabs(a.tinitial) + fabs(m.tfinal));
-                    if ((t_lower - a.tinitial) < -tfuzz || (m.tfinal - t_lower) < -tfuzz) status = CV_ILL_INPUT;
+                if (status == CV_SUCCESS && ((t_lower - SA_TINIT(a, inst)) < 0.0 || (m.tfinal - t_lower) < 0.0)) {
+                    double tfuzz = 100.0 * UROUND * (fabs(SA_TINIT(a, inst)) + fabs(m.tfinal));
+                    if ((t_lower - SA_TINIT(a, inst)) < -tfuzz || (m.tfinal - t_lower) < -tfuzz) status = CV_ILL_INPUT;
                 }
                 if (status == CV_SUCCESS) {
                     int flag = cv_first_call(m, t_lower);
@@ -756,11 +764,16 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_backward(sa_bwd_args a)
     st[ST_RETRIES] = total_retries; st[ST_ATTEMPTS] = attempts;
     SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
 }
+extern "C" __global__ void __launch_bounds__(64) sa_k_backward(sa_bwd_args a) { k_backward<false>(a); }
+extern "C" __global__ void __launch_bounds__(64) sa_k_backward_t(sa_bwd_args a) { k_backward<true>(a); }
 
 #ifdef SA_SENS
 /* Solver(sens_mode).solve (reference solver.py:467-527): CVodeReInit + CVodeSensReInit, then per output
    time CVode(NORMAL) with the mxstep x max_retries budget, CVodeGetSens */
-extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_sens(const sa_sens_args &a)
 {
     const int inst = blockIdx.x * 64 + threadIdx.x;
     if (inst >= a.B) return;
@@ -772,7 +785,7 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
 
     const Vec y0{const_cast<double *>(a.y0) + (int64_t)inst * NS, 1};
     const double *s0 = a.sens0 + (int64_t)inst * NQ * NS;
-    cv_reinit(m, a.t0, y0, wvec(m, O_QUAD));
+    cv_reinit(m, SA_T0(a, inst), y0, wvec(m, O_QUAD));
     for (int v = 0; v < SV_COUNT; v++)
         for (int is = 0; is < NQ; is++)
             for (int i = 0; i < NS; i++) SV(m, v, is, i) = (v == SV_ZN0) ? s0[is * NS + i] : 0.0;
@@ -780,7 +793,7 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     double *yo = a.y_out + (int64_t)inst * a.n_t * NS;
     double *so = a.sens_out + (int64_t)inst * a.n_t * NQ * NS;
     int status = CV_SUCCESS, k = 0, nstloc = 0, retries = 0, total_retries = 0, attempts = 0;
-    while (k < a.n_t && a.tvals[k] == a.t0) {
+    while (k < a.n_t && SA_TV(a, inst, k) == SA_T0(a, inst)) {
         for (int i = 0; i < NS; i++) yo[(int64_t)k * NS + i] = y0[i];
         for (int j = 0; j < NQ * NS; j++) so[(int64_t)k * NQ * NS + j] = s0[j];
         k++;
@@ -788,9 +801,9 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     bool done = (k >= a.n_t);
     StepCtl c;
     c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.ncfS = c.nefS = 0; c.convfail = 0;
-    c.saved_t = a.t0;
+    c.saved_t = SA_T0(a, inst);
     if (!done) {
-        int flag = cv_first_call(m, a.tvals[k]);
+        int flag = cv_first_call(m, SA_TV(a, inst, k));
         if (flag != CV_SUCCESS) { status = flag; done = true; }
     }
     while (!done) {
@@ -811,8 +824,8 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
             else if (r == 1) {
                 nstloc++;
                 while (!done && k < a.n_t) {
-                    double tout = a.tvals[k];
-                    if (tout == a.t0) {
+                    double tout = SA_TV(a, inst, k);
+                    if (tout == SA_T0(a, inst)) {
                         for (int i = 0; i < NS; i++) yo[(int64_t)k * NS + i] = y0[i];
                         for (int j = 0; j < NQ * NS; j++) so[(int64_t)k * NQ * NS + j] = s0[j];
                         k++;
@@ -851,6 +864,8 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     st[ST_RETRIES] = total_retries; st[ST_ATTEMPTS] = attempts;
     SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
 }
+extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a) { k_sens<false>(a); }
+extern "C" __global__ void __launch_bounds__(64) sa_k_sens_t(sa_sens_args a) { k_sens<true>(a); }
 #endif
 
 /* callback evaluation + arithmetic probe (plain arrays, unit stride) */

@@ -2523,7 +2523,10 @@ DEV void store_table(double *rec, int lane, int order, double dt, const double (
 }
 
 /* ------------------------------------------------------------------------------------ */
-extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_forward(sa_fwd_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_forward(const sa_fwd_args &a)
 {
     const int inst = blockIdx.x * KPW + sa_grp();
     if (inst >= a.B) return;
@@ -2548,7 +2551,7 @@ extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_forward(sa_fwd_
     double y0[RS], q0[RQ];
     SFOR(r, 0, RS) y0[r] = (IDX(m, r) < NS) ? a.y0[(int64_t)inst * NS + (IDX(m, r) < NS ? IDX(m, r) : 0)] : 0.0; SEND
     SFOR(r, 0, RQ) q0[r] = 0.0; SEND
-    cv_reinit(m, a.t0, y0, q0);
+    cv_reinit(m, SA_T0(a, inst), y0, q0);
 
     /* store: CVodeF semantics (every step is a data point, no mxstep budget); wr: the points are written to the
        arena (SA_MODE_ADJ_COUNT runs the identical pass and only counts them, see sunode_amd.cpp) */
@@ -2560,15 +2563,15 @@ extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_forward(sa_fwd_
     SFOR(j, 0, (QMAX) + 1) { hT[j] = 0.0; SFOR(r, 0, RS) hY[j][r] = 0.0; SEND } SEND
 
     int status = CV_SUCCESS, k = 0, np = 0, nstloc = 0, retries = 0, total_retries = 0, attempts = 0;
-    while (k < a.n_t && a.tvals[k] == a.t0) {
+    while (k < a.n_t && SA_TV(a, inst, k) == SA_T0(a, inst)) {
         SFOR(r, 0, RS) { if (IDX(m, r) < NS) yo[(int64_t)k * NS + IDX(m, r)] = y0[r]; } SEND
         k++;
     }
     bool done = (k >= a.n_t);
     StepCtl c;
-    c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.ncfS = c.nefS = 0; c.convfail = 0; c.saved_t = a.t0;
+    c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.ncfS = c.nefS = 0; c.convfail = 0; c.saved_t = SA_T0(a, inst);
     if (!done) {
-        int flag = cv_first_call(m, a.tvals[k]);
+        int flag = cv_first_call(m, SA_TV(a, inst, k));
         if (flag != CV_SUCCESS) { status = flag; done = true; }
         else if (store) {
             hT[0] = m.tn;
@@ -2623,8 +2626,8 @@ extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_forward(sa_fwd_
                     }
                 }
                 while (!done && k < a.n_t) {
-                    double tout = a.tvals[k];
-                    if (tout == a.t0) {
+                    double tout = SA_TV(a, inst, k);
+                    if (tout == SA_T0(a, inst)) {
                         SFOR(s, 0, RS) { if (IDX(m, s) < NS) yo[(int64_t)k * NS + IDX(m, s)] = y0[s]; } SEND
                         k++;
                     } else if ((m.tn - tout) * m.h >= 0.0) {
@@ -2662,12 +2665,17 @@ extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_forward(sa_fwd_
         SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
     }
 }
+extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_forward(sa_fwd_args a) { k_forward<false>(a); }
+extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_forward_t(sa_fwd_args a) { k_forward<true>(a); }
 
 #ifdef SA_SENS
 /* Solver(sens_mode=...).solve (reference solver.py:360-392, 497-531) in the lean lane groups: the forward problem
    together with its NQ sensitivity systems.  Same control flow as sa_k_forward without the trajectory; bit-identical
    to the register kernel's / bdf_mem.hip's sa_k_sens (and to the oracle). */
-extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_sens(const sa_sens_args &a)
 {
     const int inst = blockIdx.x * KPW + sa_grp();
     if (inst >= a.B) return;
@@ -2689,7 +2697,7 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     double y0[RS], q0[RQ];
     SFOR(r, 0, RS) y0[r] = (IDX(m, r) < NS) ? a.y0[(int64_t)inst * NS + (IDX(m, r) < NS ? IDX(m, r) : 0)] : 0.0; SEND
     SFOR(r, 0, RQ) q0[r] = 0.0; SEND
-    cv_reinit(m, a.t0, y0, q0);
+    cv_reinit(m, SA_T0(a, inst), y0, q0);
     const double *s0 = a.sens0 + (int64_t)inst * NQ * NS;
     for (int v = 0; v < SV_COUNT; v++)
         SLOOP_BEGIN(is) SFOR(r, 0, RS) SV(m, v, is, r) = (v == SV_ZN0 && IDX(m, r) < NS) ? s0[is * NS + (IDX(m, r) < NS ? IDX(m, r) : 0)] : 0.0; SEND SLOOP_END
@@ -2697,7 +2705,7 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     double *yo = a.y_out + (int64_t)inst * a.n_t * NS;
     double *so = a.sens_out + (int64_t)inst * a.n_t * NQ * NS;
     int status = CV_SUCCESS, k = 0, nstloc = 0, retries = 0, total_retries = 0, attempts = 0;
-    while (k < a.n_t && a.tvals[k] == a.t0) {
+    while (k < a.n_t && SA_TV(a, inst, k) == SA_T0(a, inst)) {
         SFOR(r, 0, RS) { if (IDX(m, r) < NS) yo[(int64_t)k * NS + IDX(m, r)] = y0[r]; } SEND
         SLOOP_BEGIN(is) SFOR(r, 0, RS) { if (IDX(m, r) < NS) so[((int64_t)k * NQ + is) * NS + IDX(m, r)] = s0[is * NS + IDX(m, r)]; } SEND SLOOP_END
         k++;
@@ -2705,9 +2713,9 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
     bool done = (k >= a.n_t);
     StepCtl c;
     c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.ncfS = c.nefS = 0; c.convfail = 0;
-    c.saved_t = a.t0;
+    c.saved_t = SA_T0(a, inst);
     if (!done) {
-        int flag = cv_first_call(m, a.tvals[k]);
+        int flag = cv_first_call(m, SA_TV(a, inst, k));
         if (flag != CV_SUCCESS) { status = flag; done = true; }
     }
     while (!done) {
@@ -2728,8 +2736,8 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
             else if (r == 1) {
                 nstloc++;
                 while (!done && k < a.n_t) {
-                    double tout = a.tvals[k];
-                    if (tout == a.t0) {
+                    double tout = SA_TV(a, inst, k);
+                    if (tout == SA_T0(a, inst)) {
                         SFOR(s, 0, RS) { if (IDX(m, s) < NS) yo[(int64_t)k * NS + IDX(m, s)] = y0[s]; } SEND
                         SLOOP_BEGIN(is) SFOR(s, 0, RS) { if (IDX(m, s) < NS) so[((int64_t)k * NQ + is) * NS + IDX(m, s)] = s0[is * NS + IDX(m, s)]; } SEND SLOOP_END
                         k++;
@@ -2773,9 +2781,14 @@ extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a)
         SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
     }
 }
+extern "C" __global__ void __launch_bounds__(64) sa_k_sens(sa_sens_args a) { k_sens<false>(a); }
+extern "C" __global__ void __launch_bounds__(64) sa_k_sens_t(sa_sens_args a) { k_sens<true>(a); }
 #endif
 
-extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_backward(sa_bwd_args a)
+/* the kernel body for both launch forms: SA_PT = per-instance start times / output grids (sa_*_batch_times;
+   sa_common.h SA_T0 ...), the shared-time kernel otherwise */
+template <bool SA_PT>
+DEV void k_backward(const sa_bwd_args &a)
 {
     const int inst = blockIdx.x * KPW + sa_grp();
     if (inst >= a.B) return;
@@ -2800,11 +2813,11 @@ extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_backward(sa_bwd
     m.rtol = a.rtolB;
     SFOR(r, 0, RS) m.atol[r] = a.atolB; SEND
     m.rtolQ = a.rtolQB; m.atolQ = a.atolQB;
-    m.tstop = a.tinitial;
+    m.tstop = SA_TINIT(a, inst);
     m.traj = a.traj + (int64_t)inst * a.traj_istride * TREC;
     m.trow = a.traj_stride * TREC;
     m.np = np;
-    m.tfinal = (status == CV_SUCCESS) ? m.traj[(int64_t)(np - 1) * m.trow + TREC_T] : a.tinitial;
+    m.tfinal = (status == CV_SUCCESS) ? m.traj[(int64_t)(np - 1) * m.trow + TREC_T] : SA_TINIT(a, inst);
     m.cur_idx = 0; m.tlo2 = 0.0; m.tlo = m.thi = 0.0;
     m.ilast = 0; m.newdata = 1; m.have_last = 0; m.last_t = 0.0;
     m.n_interp = 0; m.n_rebuild = 0;
@@ -2815,15 +2828,15 @@ extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_backward(sa_bwd
         SFOR(r, 0, RS) { lam0[r] = 0.0; if (IDX(m, r) < NS) lam_g[IDX(m, r)] = 0.0; } SEND
         SFOR(r, 0, RQ) { quad0[r] = 0.0; if (IDX(m, r) < NQ) quad_g[IDX(m, r)] = 0.0; } SEND
         if (m.li == 0) { SFOR(i, 0, SA_N_STATS) strow[i] = 0; SEND }
-        cv_reinit(m, a.t0, lam0, quad0);
+        cv_reinit(m, SA_T0(a, inst), lam0, quad0);
     }
     const double *g = a.grads + (int64_t)inst * a.grads_stride;
     bool first_call = true;
     int total_retries = 0, attempts = 0;
 
     for (int iv = 0; iv <= a.n_t; iv++) {
-        const double t_upper = (iv == 0) ? a.t0 : a.tvals[a.n_t - iv];
-        const double t_lower = (iv == a.n_t) ? a.tend : a.tvals[a.n_t - 1 - iv];
+        const double t_upper = (iv == 0) ? SA_T0(a, inst) : SA_TV(a, inst, a.n_t - iv);
+        const double t_lower = (iv == a.n_t) ? SA_TEND(a, inst) : SA_TV(a, inst, a.n_t - 1 - iv);
         if (t_lower < t_upper) {
             if (status == CV_SUCCESS) {
                 {
@@ -2833,12 +2846,12 @@ extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_backward(sa_bwd
                     cv_reinit(m, t_upper, lam, quad);
                 }
                 if (first_call) {
-                    if ((t_upper - a.tinitial) < 0.0 || (m.tfinal - t_upper) < 0.0) status = CV_BAD_TB0;
+                    if ((t_upper - SA_TINIT(a, inst)) < 0.0 || (m.tfinal - t_upper) < 0.0) status = CV_BAD_TB0;
                     first_call = false;
                 }
-                if (status == CV_SUCCESS && ((t_lower - a.tinitial) < 0.0 || (m.tfinal - t_lower) < 0.0)) {
-                    double tfuzz = 100.0 * UROUND * (fabs(a.tinitial) + fabs(m.tfinal));
-                    if ((t_lower - a.tinitial) < -tfuzz || (m.tfinal - t_lower) < -tfuzz) status = CV_ILL_INPUT;
+                if (status == CV_SUCCESS && ((t_lower - SA_TINIT(a, inst)) < 0.0 || (m.tfinal - t_lower) < 0.0)) {
+                    double tfuzz = 100.0 * UROUND * (fabs(SA_TINIT(a, inst)) + fabs(m.tfinal));
+                    if ((t_lower - SA_TINIT(a, inst)) < -tfuzz || (m.tfinal - t_lower) < -tfuzz) status = CV_ILL_INPUT;
                 }
                 if (status == CV_SUCCESS) {
                     PH_T0
@@ -2946,6 +2959,8 @@ extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_backward(sa_bwd
         SFOR(i, 0, SA_N_STATS) a.stats[(int64_t)inst * SA_N_STATS + i] = st[i]; SEND
     }
 }
+extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_backward(sa_bwd_args a) { k_backward<false>(a); }
+extern "C" __global__ void __launch_bounds__(64 * SA_WAVES) sa_k_backward_t(sa_bwd_args a) { k_backward<true>(a); }
 
 /* callback evaluation: the host launches ceil(npts/64) blocks; a block walks its 64 points with
    the whole wave (inputs staged in LDS exactly as in the integrator) */

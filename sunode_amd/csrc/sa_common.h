@@ -17,6 +17,14 @@
 /* explicit fused multiply-add at the same places as the CPU oracle (no compiler contraction) */
 #define FMA(a, b, c) __builtin_fma((a), (b), (c))
 
+/* Times of instance `inst` in a kernel body template<bool SA_PT> (sa_device_abi.h): the shared scalars and grid of the
+   plain entry points, or -- SA_PT, the sa_*_batch_times launches -- the instance's own entry of the [B] arrays and row
+   of the grid (tvals_stride 0: the shared grid).  Read where used, not held in registers across the step loop. */
+#define SA_T0(a, inst) (SA_PT ? (a).t0s[inst] : (a).t0)
+#define SA_TEND(a, inst) (SA_PT ? (a).tends[inst] : (a).tend)
+#define SA_TINIT(a, inst) (SA_PT ? (a).tinits[inst] : (a).tinitial)
+#define SA_TV(a, inst, k) (SA_PT ? (a).tvals[(int64_t)(inst) * (a).tvals_stride + (k)] : (a).tvals[k])
+
 /*
  * Compile-time loops.  Every per-lane array (Nordsieck columns, LU, coefficient vectors...) must
  * be scalar-replaced into VGPRs by the FIRST SROA pass, i.e. before instcombine gets a chance to

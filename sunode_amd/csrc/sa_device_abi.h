@@ -7,7 +7,10 @@
  *                             a leading batch axis; reference solver.py:682)
  *   ps      [B][p]            differentiated parameters, subset_paths order
  *   pr      [B][r] or [r]     remaining parameters (rem_stride = r or 0)
- *   tvals   [n_t]             shared output grid
+ *   tvals   [n_t]             shared output grid; the per-instance kernels (sa_k_*_t, sa_*_batch_times) read
+ *                             row inst * tvals_stride of [B][n_t] (tvals_stride = n_t) or the shared grid (0), and
+ *                             the start / end times from the [B] arrays t0s / tends / tinits instead of the scalars
+ *                             t0 / tend / tinitial (sa_common.h SA_T0 / SA_TEND / SA_TINIT / SA_TV)
  *   y_out   [B][n_t][n]
  *   grads   [B][n_t][n] or [n_t][n] (grads_stride = n_t*n or 0)
  *   stats   [B][16] int64     counters, see SA_ST_* in include/sunode_amd.h
@@ -49,7 +52,7 @@ typedef struct {
     int32_t B, n_t, mode, mxstep, max_retries, traj_cap, rem_stride, traj_istride;
     int64_t traj_stride;      /* record (instance i, point s) at traj + (i * traj_istride + s * traj_stride) * record size */
     int32_t traj_max;         /* store modes: most points an instance may produce (SA_TRAJ_FULL beyond) */
-    int32_t reserved0;
+    int32_t tvals_stride;     /* 0 or n_t (per-instance kernels) */
     int32_t *overflow;        /* store modes: atomic max of the point counts of instances with more than traj_cap points */
     double t0, rtol;
     const double *atol;
@@ -62,10 +65,11 @@ typedef struct {
     double *ws;               /* memory-resident kernels only: [sa_meta[5]][ws_stride] doubles */
     int64_t ws_stride;
     const double *constraints; /* [n] CVodeSetConstraints vector or NULL (read by SA_CONSTRAINTS builds only) */
+    const double *t0s;        /* [B] start times (per-instance kernels) */
 } sa_fwd_args;
 
 typedef struct {
-    int32_t B, n_t, mxstep, max_retries, traj_cap, rem_stride, traj_istride, reserved1;
+    int32_t B, n_t, mxstep, max_retries, traj_cap, rem_stride, traj_istride, tvals_stride;
     int64_t traj_stride, grads_stride;
     double t0, tend, tinitial;
     double rtolB, atolB, rtolQB, atolQB;
@@ -82,6 +86,8 @@ typedef struct {
        [B][n_t][n] / [B][n_t][p] with the reference's row order (solver.py:778-781 writes row -i for the
        i-th jump counted from the last output time, i.e. row 0, n_t-1, n_t-2, ..., 1) */
     double *lamda_all, *quad_all;
+    /* per-instance kernels: [B] final / initial times of the backward pass and start times of the forward pass */
+    const double *t0s, *tends, *tinits;
 } sa_bwd_args;
 
 /* Solver(sens_mode=...).solve: forward solve + forward sensitivities (SA_SENS build of bdf_mem.hip).
@@ -89,7 +95,7 @@ typedef struct {
    as the reference's sens_out[i, j, :], solver.py:527); ism 0 = simultaneous, 1 = staggered corrector;
    pbar [p] = |scaling_factors| (ones by default). */
 typedef struct {
-    int32_t B, n_t, ism, mxstep, max_retries, rem_stride, reserved0, reserved1;
+    int32_t B, n_t, ism, mxstep, max_retries, rem_stride, tvals_stride, reserved1;
     double t0, rtol;
     const double *atol, *pbar;
     const double *y0, *ps, *pr, *sens0, *tvals;
@@ -98,6 +104,7 @@ typedef struct {
     int64_t *stats;
     double *ws;
     int64_t ws_stride;
+    const double *t0s;        /* [B] start times (per-instance kernels) */
 } sa_sens_args;
 
 typedef struct {

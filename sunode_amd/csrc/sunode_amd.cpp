@@ -95,6 +95,7 @@ struct sa_solver {
     hipModule_t module = nullptr;
     hipFunction_t k_forward = nullptr, k_backward = nullptr, k_eval = nullptr, k_math = nullptr;
     hipFunction_t k_sens = nullptr;            /* only in forward-sensitivity builds */
+    hipFunction_t k_forward_t = nullptr, k_backward_t = nullptr, k_sens_t = nullptr;   /* per-instance times */
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   /* fwd start/stop, bwd start/stop */
@@ -111,10 +112,16 @@ struct sa_solver {
     int32_t traj_rows = 0;         /* rows the resident arena was launched with */
     int32_t fwd_B = 0;
     double fwd_t0 = 0.0;
+    bool fwd_pt = false;           /* the forward call had per-instance times: keep_t0 [B] holds its start times */
+    int32_t fwd_tvals_stride = 0;  /* 0: keep_tvals is the shared grid, n_t: one row per instance */
+    std::vector<double> h_fill;    /* a shared time spread over the batch for a per-instance launch */
     bool tiled = false;            /* the trajectories are NOT resident: the backward call re-integrates tile by tile */
     std::vector<int32_t> h_np;     /* tiled mode: points per instance, from the counting pass */
     std::vector<int32_t> h_scratch;
-    DevBuf keep_y0, keep_tvals;    /* tiled mode: the forward call's initial states and output grid */
+    DevBuf keep_y0, keep_tvals;    /* tiled mode: the forward call's initial states and output grid(s) */
+    DevBuf keep_t0;                /* per-instance start times of the forward call (the backward kernel's tinitial) */
+    DevBuf s_tinit;                /* ... spread from the scalar when a shared-time forward call meets a per-instance
+                                      backward call */
     int32_t fwd_n_t = 0;
     DevBuf t_yout, t_status, t_stats, t_np;   /* outputs of the re-integration (discarded: identical to the forward call's) */
     int32_t rows_hint = 0;         /* largest per-instance point count seen so far on this handle */
@@ -127,7 +134,7 @@ struct sa_solver {
     std::vector<int32_t> full_idx; /* instances whose 64-instance group exceeds the budget: backward status ARENA_FULL */
     int64_t stat_tiles = 0, stat_arena_bytes = 0;
     /* staging for SA_MEM_HOST calls */
-    DevBuf s_y0, s_ps, s_pr, s_tvals, s_yout, s_status, s_stats, s_grads, s_gout, s_lout;
+    DevBuf s_y0, s_ps, s_pr, s_tvals, s_yout, s_status, s_stats, s_grads, s_gout, s_lout, s_t0, s_tend;
     DevBuf s_misc[12];
 };
 
@@ -250,9 +257,9 @@ extern "C" int sa_solver_create(const char *path, const sa_options *opt, sa_solv
         const char *force = getenv("SA_TRAJ_LAYOUT");
         if (force && !s->point_major) s->point_major = (force[0] == 'p');
     }
-    const char *names[4] = {"sa_k_forward", "sa_k_backward", "sa_k_eval", "sa_k_math"};
-    hipFunction_t *slots[4] = {&s->k_forward, &s->k_backward, &s->k_eval, &s->k_math};
-    for (int i = 0; i < 4; i++) {
+    const char *names[6] = {"sa_k_forward", "sa_k_backward", "sa_k_eval", "sa_k_math", "sa_k_forward_t", "sa_k_backward_t"};
+    hipFunction_t *slots[6] = {&s->k_forward, &s->k_backward, &s->k_eval, &s->k_math, &s->k_forward_t, &s->k_backward_t};
+    for (int i = 0; i < 6; i++) {
         e = hipModuleGetFunction(slots[i], s->module, names[i]);
         if (e != hipSuccess) {
             (void)hipModuleUnload(s->module);
@@ -260,8 +267,9 @@ extern "C" int sa_solver_create(const char *path, const sa_options *opt, sa_solv
             return fail(SA_ERR_MODULE, "%s: kernel %s not found", path, names[i]);
         }
     }
-    if (hipModuleGetFunction(&s->k_sens, s->module, "sa_k_sens") != hipSuccess) {
-        s->k_sens = nullptr;
+    if (hipModuleGetFunction(&s->k_sens, s->module, "sa_k_sens") != hipSuccess ||
+        hipModuleGetFunction(&s->k_sens_t, s->module, "sa_k_sens_t") != hipSuccess) {
+        s->k_sens = s->k_sens_t = nullptr;
         (void)hipGetLastError();     /* the optional kernel is absent: do not leave hipErrorNotFound behind for
                                         other users of the runtime in this process (PyTorch checks it) */
     }
@@ -287,7 +295,8 @@ extern "C" void sa_solver_destroy(sa_solver *s)
     DeviceScope scope(s->device);
     guard_free(s);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    DevBuf *bufs[] = {&s->d_atol, &s->traj, &s->traj_np, &s->fwd_status, &s->keep_y0, &s->keep_tvals,
+    DevBuf *bufs[] = {&s->d_atol, &s->traj, &s->traj_np, &s->fwd_status, &s->keep_y0, &s->keep_tvals, &s->keep_t0,
+                      &s->s_t0, &s->s_tend, &s->s_tinit,
                       &s->t_yout, &s->t_status, &s->t_stats, &s->t_np, &s->s_y0,
                       &s->s_ps, &s->s_pr, &s->s_tvals, &s->s_yout, &s->s_status, &s->s_stats, &s->s_grads,
                       &s->s_gout, &s->s_lout, &s->ws, &s->d_constraints, &s->d_overflow};
@@ -439,7 +448,33 @@ static size_t record_bytes(const sa_solver *s) { return sizeof(double) * (size_t
 struct FwdLaunch {
     int mode; int32_t B, n_t, rem_stride, rows; int64_t stride; double t0;
     const double *y0, *ps, *pr, *tvals; double *y_out; int32_t *status; int64_t *stats; int32_t *traj_np;
+    const double *t0s = nullptr; int32_t tvals_stride = 0;
+    bool pt = false;           /* the per-instance kernel (t0s [B]) */
 };
+
+/* Per-instance times of a batch call (the sa_*_batch_times entry points): [B] start / end times (NULL: the shared
+   scalar) and the stride of the grid rows (0: the shared grid) -- what the plain entry points pass is all-NULL / 0.
+   Pointers live where the call's `mem` says until staged; from the launch on they are device pointers. */
+struct Times {
+    const double *t0s = nullptr, *tends = nullptr;
+    int32_t tvals_stride = 0;
+    bool on = false;           /* per-instance call: the *_t kernels, every time array [B] on the device */
+};
+
+/* [B] device array of a shared time for a per-instance launch (rare: a scalar t0 beside a [B, n_t] grid and the like) */
+static int spread_time(sa_solver *s, DevBuf &b, double v, size_t nB, const double **dev)
+{
+    s->h_fill.assign(nB ? nB : 1, v);
+    const void *q;
+    int rc = stage_in(s, b, s->h_fill.data(), sizeof(double) * s->h_fill.size(), &q);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));      /* (h_fill is reused by the next spread) */
+    *dev = (const double *)q;
+    return SA_OK;
+}
+
+/* doubles of the output grid(s) of a B-instance call */
+static size_t tv_count(int32_t tvals_stride, int32_t n_t, size_t nB) { return (size_t)n_t * (tvals_stride ? nB : 1); }
 
 static int launch_forward(sa_solver *s, const FwdLaunch &f)
 {
@@ -450,6 +485,7 @@ static int launch_forward(sa_solver *s, const FwdLaunch &f)
     a.traj_max = s->opt.traj_capacity; a.overflow = (int32_t *)s->d_overflow.p;
     a.t0 = f.t0; a.rtol = s->opt.rtol; a.atol = (const double *)s->d_atol.p;
     a.y0 = f.y0; a.ps = f.ps; a.pr = f.pr; a.tvals = f.tvals; a.y_out = f.y_out; a.status = f.status; a.stats = f.stats;
+    a.t0s = f.t0s; a.tvals_stride = f.tvals_stride;
     a.constraints = s->have_constraints ? (const double *)s->d_constraints.p : nullptr;
     /* arena layout: the register / lane-group / workgroup kernels keep every instance's records contiguous
        ([instance][point]: the backward pass walks an instance's points in order, so consecutive records share cache
@@ -459,27 +495,27 @@ static int launch_forward(sa_solver *s, const FwdLaunch &f)
     a.traj = (double *)s->traj.p; a.traj_np = f.traj_np;
     int rc;
     if ((rc = bind_workspace(s, f.B, &a.ws, &a.ws_stride))) return rc;
-    return launch(s, s->k_forward, f.B, &a, sizeof a, s->group);
+    return launch(s, f.pt ? s->k_forward_t : s->k_forward, f.B, &a, sizeof a, s->group);
 }
 
 static int guard_forward(sa_solver *s, int mode, int32_t B, const double *d_y0, const double *d_ps, const double *d_pr,
                          int32_t rem_stride, double t0, const double *d_tv, int32_t n_t, const int32_t *d_status,
-                         const int64_t *d_stats);
+                         const int64_t *d_stats, const Times &tm, const double *d_yout);
 static bool guard_wants(const sa_solver *s, uint32_t kind);
 static bool guard_recheck_due(sa_solver *s, uint32_t kind, int32_t B, const int32_t *status, const int64_t *stats);
 static bool guard_switched(sa_solver *s);
 
 static int forward_common(sa_solver *s, int mode, int mem, int32_t B, const double *y0, const double *ps,
                           const double *pr, int32_t rem_stride, double t0, const double *tvals, int32_t n_t,
-                          double *y_out, int32_t *status, int64_t *stats)
+                          double *y_out, int32_t *status, int64_t *stats, const Times &tm = Times())
 {
     if (!s) return fail(SA_ERR_ARG, "null solver");
     if (B < 0 || n_t < 0) return fail(SA_ERR_ARG, "negative size");
     if (rem_stride != 0 && rem_stride != s->r) return fail(SA_ERR_ARG, "rem_stride must be 0 or n_rem=%d", s->r);
     HIP_TRY(hipSetDevice(s->device));
     if (B == 0 || n_t == 0) return SA_OK;
-    const size_t nB = (size_t)B;
-    const double *d_y0 = y0, *d_ps = ps, *d_pr = pr, *d_tv = tvals;
+    const size_t nB = (size_t)B, n_tv = tv_count(tm.tvals_stride, n_t, nB), n_t0 = nB;
+    const double *d_y0 = y0, *d_ps = ps, *d_pr = pr, *d_tv = tvals, *d_t0s = tm.t0s;
     double *d_yout = y_out;
     int32_t *d_status = status;
     int64_t *d_stats = stats;
@@ -489,7 +525,8 @@ static int forward_common(sa_solver *s, int mode, int mem, int32_t B, const doub
         if ((rc = stage_in(s, s->s_y0, y0, sizeof(double) * nB * s->n, &q))) return rc; d_y0 = (const double *)q;
         if ((rc = stage_in(s, s->s_ps, ps, sizeof(double) * nB * s->p, &q))) return rc; d_ps = (const double *)q;
         if ((rc = stage_in(s, s->s_pr, pr, sizeof(double) * (rem_stride ? nB : 1) * s->r, &q))) return rc; d_pr = (const double *)q;
-        if ((rc = stage_in(s, s->s_tvals, tvals, sizeof(double) * n_t, &q))) return rc; d_tv = (const double *)q;
+        if ((rc = stage_in(s, s->s_tvals, tvals, sizeof(double) * n_tv, &q))) return rc; d_tv = (const double *)q;
+        if (tm.t0s) { if ((rc = stage_in(s, s->s_t0, tm.t0s, sizeof(double) * n_t0, &q))) return rc; d_t0s = (const double *)q; }
         if ((rc = s->s_yout.ensure(sizeof(double) * nB * n_t * s->n))) return rc; d_yout = (double *)s->s_yout.p;
         if ((rc = s->s_status.ensure(sizeof(int32_t) * nB))) return rc; d_status = (int32_t *)s->s_status.p;
         if ((rc = s->s_stats.ensure(sizeof(int64_t) * nB * SA_N_STATS))) return rc; d_stats = (int64_t *)s->s_stats.p;
@@ -497,7 +534,9 @@ static int forward_common(sa_solver *s, int mode, int mem, int32_t B, const doub
         return fail(SA_ERR_ARG, "mem must be SA_MEM_HOST or SA_MEM_DEVICE");
     }
     const uint32_t gkind = mode == SA_MODE_PLAIN ? SA_GUARD_PLAIN : SA_GUARD_ADJOINT;
-    FwdLaunch f{mode, B, n_t, rem_stride, 2, 0, t0, d_y0, d_ps, d_pr, d_tv, d_yout, d_status, d_stats, nullptr};
+    if (tm.on && !d_t0s && (rc = spread_time(s, s->s_t0, t0, nB, &d_t0s))) return rc;
+    FwdLaunch f{mode, B, n_t, rem_stride, 2, 0, t0, d_y0, d_ps, d_pr, d_tv, d_yout, d_status, d_stats, nullptr,
+                d_t0s, tm.tvals_stride, tm.on};
     if (mode == SA_MODE_PLAIN) {
         HIP_TRY(hipEventRecord(s->ev[0], s->stream));
         if ((rc = launch_forward(s, f))) return rc;
@@ -519,7 +558,8 @@ static int forward_common(sa_solver *s, int mode, int mem, int32_t B, const doub
         if ((rc = s->fwd_status.ensure(sizeof(int32_t) * stride))) return rc;
         if ((rc = s->d_overflow.ensure(sizeof(int32_t)))) return rc;
         if ((rc = s->keep_y0.ensure(sizeof(double) * nB * (size_t)(s->n > 0 ? s->n : 1)))) return rc;
-        if ((rc = s->keep_tvals.ensure(sizeof(double) * (size_t)n_t))) return rc;
+        if ((rc = s->keep_tvals.ensure(sizeof(double) * n_tv))) return rc;
+        if (tm.on && (rc = s->keep_t0.ensure(sizeof(double) * n_t0))) return rc;
         f.traj_np = (int32_t *)s->traj_np.p;
         HIP_TRY(hipMemsetAsync(s->d_overflow.p, 0, sizeof(int32_t), s->stream));
         HIP_TRY(hipEventRecord(s->ev[0], s->stream));
@@ -538,12 +578,16 @@ static int forward_common(sa_solver *s, int mode, int mem, int32_t B, const doub
         if (s->keep_y0.p != (const void *)d_y0)       /* (the guard's repeat of a forward pass reads them in place) */
             HIP_TRY(hipMemcpyAsync(s->keep_y0.p, d_y0, sizeof(double) * nB * s->n, hipMemcpyDeviceToDevice, s->stream));
         if (s->keep_tvals.p != (const void *)d_tv)
-            HIP_TRY(hipMemcpyAsync(s->keep_tvals.p, d_tv, sizeof(double) * (size_t)n_t, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(s->keep_tvals.p, d_tv, sizeof(double) * n_tv, hipMemcpyDeviceToDevice, s->stream));
+        if (tm.on && s->keep_t0.p != (const void *)d_t0s)
+            HIP_TRY(hipMemcpyAsync(s->keep_t0.p, d_t0s, sizeof(double) * n_t0, hipMemcpyDeviceToDevice, s->stream));
         HIP_TRY(hipMemcpyAsync(s->fwd_status.p, d_status, sizeof(int32_t) * nB, hipMemcpyDeviceToDevice, s->stream));
         s->pending = true;
         s->tiled = !s->resident_attempt;
         s->fwd_B = B;
         s->fwd_t0 = t0;
+        s->fwd_pt = tm.on;
+        s->fwd_tvals_stride = tm.tvals_stride;
         s->fwd_n_t = n_t;
     }
     if (mem == SA_MEM_HOST) {
@@ -558,9 +602,12 @@ static int forward_common(sa_solver *s, int mode, int mem, int32_t B, const doub
        had -- goes through the default AND the conservative build: a sample chosen from the statuses and counters the
        main launch has just produced, compared bit for bit */
     if (guard_wants(s, gkind) || (mem == SA_MEM_HOST && guard_recheck_due(s, gkind, B, status, stats))) {
-        if ((rc = guard_forward(s, mode, B, d_y0, d_ps, d_pr, rem_stride, t0, d_tv, n_t, d_status, d_stats))) return rc;
+        Times dtm = tm;
+        dtm.t0s = d_t0s;
+        if ((rc = guard_forward(s, mode, B, d_y0, d_ps, d_pr, rem_stride, t0, d_tv, n_t, d_status, d_stats, dtm, d_yout)))
+            return rc;
         if (guard_switched(s))      /* the builds differ: THIS batch again, with the conservative code object */
-            return forward_common(s, mode, mem, B, y0, ps, pr, rem_stride, t0, tvals, n_t, y_out, status, stats);
+            return forward_common(s, mode, mem, B, y0, ps, pr, rem_stride, t0, tvals, n_t, y_out, status, stats, tm);
     }
     return SA_OK;
 }
@@ -574,12 +621,12 @@ extern "C" int sa_solve_batch(sa_solver *s, int mem, int32_t B, const double *y0
 
 static int guard_sens(sa_solver *s, int ism, const double *scaling, int32_t B, const double *d_y0, const double *d_ps,
                       const double *d_pr, int32_t rem_stride, const double *d_s0, double t0, const double *d_tv,
-                      int32_t n_t, const int32_t *d_status, const int64_t *d_stats);
+                      int32_t n_t, const int32_t *d_status, const int64_t *d_stats, const Times &tm, const double *d_yout);
 
-extern "C" int sa_solve_sens_batch(sa_solver *s, int mem, int ism, const double *scaling, int32_t B,
-                                   const double *y0, const double *ps, const double *pr, int32_t rem_stride,
-                                   const double *sens0, double t0, const double *tvals, int32_t n_t,
-                                   double *y_out, double *sens_out, int32_t *status, int64_t *stats)
+static int sens_common(sa_solver *s, int mem, int ism, const double *scaling, int32_t B, const double *y0,
+                       const double *ps, const double *pr, int32_t rem_stride, const double *sens0, double t0,
+                       const double *tvals, int32_t n_t, double *y_out, double *sens_out, int32_t *status,
+                       int64_t *stats, const Times &tm)
 {
     if (!s) return fail(SA_ERR_ARG, "null solver");
     if (!s->k_sens) return fail(SA_ERR_ARG, "this code object was built without forward-sensitivity support");
@@ -589,9 +636,10 @@ extern "C" int sa_solve_sens_batch(sa_solver *s, int mem, int ism, const double 
     HIP_TRY(hipSetDevice(s->device));
     if (B == 0 || n_t == 0) return SA_OK;
     const size_t nB = (size_t)B, np_n = (size_t)s->p * s->n;
+    const size_t n_tv = tv_count(tm.tvals_stride, n_t, nB), n_t0 = nB;
     std::vector<double> pbar((size_t)(s->p > 0 ? s->p : 1), 1.0);
     if (scaling) for (int i = 0; i < s->p; i++) pbar[i] = scaling[i] < 0 ? -scaling[i] : scaling[i];
-    const double *d_y0 = y0, *d_ps = ps, *d_pr = pr, *d_tv = tvals, *d_s0 = sens0;
+    const double *d_y0 = y0, *d_ps = ps, *d_pr = pr, *d_tv = tvals, *d_s0 = sens0, *d_t0s = tm.t0s;
     double *d_yout = y_out, *d_sout = sens_out;
     int32_t *d_status = status;
     int64_t *d_stats = stats;
@@ -603,7 +651,8 @@ extern "C" int sa_solve_sens_batch(sa_solver *s, int mem, int ism, const double 
         if ((rc = stage_in(s, s->s_y0, y0, sizeof(double) * nB * s->n, &q))) return rc; d_y0 = (const double *)q;
         if ((rc = stage_in(s, s->s_ps, ps, sizeof(double) * nB * s->p, &q))) return rc; d_ps = (const double *)q;
         if ((rc = stage_in(s, s->s_pr, pr, sizeof(double) * (rem_stride ? nB : 1) * s->r, &q))) return rc; d_pr = (const double *)q;
-        if ((rc = stage_in(s, s->s_tvals, tvals, sizeof(double) * n_t, &q))) return rc; d_tv = (const double *)q;
+        if ((rc = stage_in(s, s->s_tvals, tvals, sizeof(double) * n_tv, &q))) return rc; d_tv = (const double *)q;
+        if (tm.t0s) { if ((rc = stage_in(s, s->s_t0, tm.t0s, sizeof(double) * n_t0, &q))) return rc; d_t0s = (const double *)q; }
         if ((rc = stage_in(s, s->s_grads, sens0, sizeof(double) * nB * np_n, &q))) return rc; d_s0 = (const double *)q;
         if ((rc = s->s_yout.ensure(sizeof(double) * nB * n_t * s->n))) return rc; d_yout = (double *)s->s_yout.p;
         if ((rc = s->s_gout.ensure(sizeof(double) * nB * n_t * (np_n ? np_n : 1)))) return rc; d_sout = (double *)s->s_gout.p;
@@ -612,16 +661,18 @@ extern "C" int sa_solve_sens_batch(sa_solver *s, int mem, int ism, const double 
     } else if (mem != SA_MEM_DEVICE) {
         return fail(SA_ERR_ARG, "mem must be SA_MEM_HOST or SA_MEM_DEVICE");
     }
+    if (tm.on && !d_t0s && (rc = spread_time(s, s->s_t0, t0, nB, &d_t0s))) return rc;
     sa_sens_args a;
     memset(&a, 0, sizeof a);
     a.B = B; a.n_t = n_t; a.ism = ism; a.mxstep = s->opt.mxstep; a.max_retries = s->opt.max_retries_fwd;
     a.rem_stride = rem_stride; a.t0 = t0; a.rtol = s->opt.rtol;
     a.atol = (const double *)s->d_atol.p; a.pbar = d_pbar;
     a.y0 = d_y0; a.ps = d_ps; a.pr = d_pr; a.sens0 = d_s0; a.tvals = d_tv;
+    a.t0s = d_t0s; a.tvals_stride = tm.tvals_stride;
     a.y_out = d_yout; a.sens_out = d_sout; a.status = d_status; a.stats = d_stats;
     if ((rc = bind_workspace(s, B, &a.ws, &a.ws_stride))) return rc;
     HIP_TRY(hipEventRecord(s->ev[0], s->stream));
-    if ((rc = launch(s, s->k_sens, B, &a, sizeof a, s->group))) return rc;
+    if ((rc = launch(s, tm.on ? s->k_sens_t : s->k_sens, B, &a, sizeof a, s->group))) return rc;
     HIP_TRY(hipEventRecord(s->ev[1], s->stream));
     s->have_fwd_time = true;
     if (mem == SA_MEM_HOST) {
@@ -633,13 +684,25 @@ extern "C" int sa_solve_sens_batch(sa_solver *s, int mem, int ism, const double 
     }
     HIP_TRY(hipStreamSynchronize(s->stream));      /* pbar staging buffer is host-owned */
     if (guard_wants(s, SA_GUARD_SENS) || (mem == SA_MEM_HOST && guard_recheck_due(s, SA_GUARD_SENS, B, status, stats))) {
-        if ((rc = guard_sens(s, ism, scaling, B, d_y0, d_ps, d_pr, rem_stride, d_s0, t0, d_tv, n_t, d_status, d_stats)))
+        Times dtm = tm;
+        dtm.t0s = d_t0s;
+        if ((rc = guard_sens(s, ism, scaling, B, d_y0, d_ps, d_pr, rem_stride, d_s0, t0, d_tv, n_t, d_status, d_stats,
+                             dtm, d_yout)))
             return rc;
         if (guard_switched(s))      /* the builds differ: THIS batch again, with the conservative code object */
-            return sa_solve_sens_batch(s, mem, ism, scaling, B, y0, ps, pr, rem_stride, sens0, t0, tvals, n_t, y_out,
-                                       sens_out, status, stats);
+            return sens_common(s, mem, ism, scaling, B, y0, ps, pr, rem_stride, sens0, t0, tvals, n_t, y_out,
+                               sens_out, status, stats, tm);
     }
     return SA_OK;
+}
+
+extern "C" int sa_solve_sens_batch(sa_solver *s, int mem, int ism, const double *scaling, int32_t B,
+                                   const double *y0, const double *ps, const double *pr, int32_t rem_stride,
+                                   const double *sens0, double t0, const double *tvals, int32_t n_t,
+                                   double *y_out, double *sens_out, int32_t *status, int64_t *stats)
+{
+    return sens_common(s, mem, ism, scaling, B, y0, ps, pr, rem_stride, sens0, t0, tvals, n_t, y_out, sens_out,
+                       status, stats, Times());
 }
 
 extern "C" int sa_solve_forward_batch(sa_solver *s, int mem, int32_t B, const double *y0, const double *ps,
@@ -694,23 +757,15 @@ static int resolve_forward(sa_solver *s)
 
 static int guard_backward(sa_solver *s, int32_t B, const double *d_ps, const double *d_pr, int32_t rem_stride,
                           double t0, double tend, const double *d_tv, int32_t n_t, const double *d_g,
-                          int64_t grads_stride);
+                          int64_t grads_stride, const Times &tm);
 static bool guard_backward_due(const sa_solver *s);
+static int guard_backward_self_check(sa_solver *s, int mem, const double *grad_out, const double *lamda_out,
+                                     const int32_t *status);
 
-extern "C" int sa_solve_backward_batch(sa_solver *s, int mem, int32_t B, const double *ps, const double *pr,
-                                       int32_t rem_stride, double t0, double tend, const double *tvals,
-                                       int32_t n_t, const double *grads, int64_t grads_stride, double *grad_out,
-                                       double *lamda_out, int32_t *status, int64_t *stats)
-{
-    return sa_solve_backward_batch_all(s, mem, B, ps, pr, rem_stride, t0, tend, tvals, n_t, grads, grads_stride,
-                                       grad_out, lamda_out, nullptr, nullptr, status, stats);
-}
-
-extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, const double *ps, const double *pr,
-                                           int32_t rem_stride, double t0, double tend, const double *tvals,
-                                           int32_t n_t, const double *grads, int64_t grads_stride,
-                                           double *grad_out, double *lamda_out, double *lamda_all_out,
-                                           double *quad_all_out, int32_t *status, int64_t *stats)
+static int backward_common(sa_solver *s, int mem, int32_t B, const double *ps, const double *pr, int32_t rem_stride,
+                           double t0, double tend, const double *tvals, int32_t n_t, const double *grads,
+                           int64_t grads_stride, double *grad_out, double *lamda_out, double *lamda_all_out,
+                           double *quad_all_out, int32_t *status, int64_t *stats, const Times &tm)
 {
     if (!s) return fail(SA_ERR_ARG, "null solver");
     if (B != s->fwd_B) return fail(SA_ERR_ARG, "backward batch %d does not match the last forward batch %d", B, s->fwd_B);
@@ -722,8 +777,8 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
         int rc0 = resolve_forward(s);
         if (rc0) return rc0;
     }
-    const size_t nB = (size_t)B;
-    const double *d_ps = ps, *d_pr = pr, *d_tv = tvals, *d_g = grads;
+    const size_t nB = (size_t)B, n_tv = tv_count(tm.tvals_stride, n_t, nB);
+    const double *d_ps = ps, *d_pr = pr, *d_tv = tvals, *d_g = grads, *d_t0s = tm.t0s, *d_tends = tm.tends;
     double *d_gout = grad_out, *d_lout = lamda_out, *d_lall = lamda_all_out, *d_qall = quad_all_out;
     int32_t *d_status = status;
     int64_t *d_stats = stats;
@@ -732,7 +787,9 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
         const void *q;
         if ((rc = stage_in(s, s->s_ps, ps, sizeof(double) * nB * s->p, &q))) return rc; d_ps = (const double *)q;
         if ((rc = stage_in(s, s->s_pr, pr, sizeof(double) * (rem_stride ? nB : 1) * s->r, &q))) return rc; d_pr = (const double *)q;
-        if ((rc = stage_in(s, s->s_tvals, tvals, sizeof(double) * n_t, &q))) return rc; d_tv = (const double *)q;
+        if ((rc = stage_in(s, s->s_tvals, tvals, sizeof(double) * n_tv, &q))) return rc; d_tv = (const double *)q;
+        if (tm.t0s) { if ((rc = stage_in(s, s->s_t0, tm.t0s, sizeof(double) * nB, &q))) return rc; d_t0s = (const double *)q; }
+        if (tm.tends) { if ((rc = stage_in(s, s->s_tend, tm.tends, sizeof(double) * nB, &q))) return rc; d_tends = (const double *)q; }
         if ((rc = stage_in(s, s->s_grads, grads, sizeof(double) * (grads_stride ? nB : 1) * n_t * s->n, &q))) return rc; d_g = (const double *)q;
         if ((rc = s->s_gout.ensure(sizeof(double) * nB * (s->p > 0 ? s->p : 1)))) return rc; d_gout = (double *)s->s_gout.p;
         if ((rc = s->s_lout.ensure(sizeof(double) * nB * (s->n > 0 ? s->n : 1)))) return rc; d_lout = (double *)s->s_lout.p;
@@ -743,8 +800,20 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
     } else if (mem != SA_MEM_DEVICE) {
         return fail(SA_ERR_ARG, "mem must be SA_MEM_HOST or SA_MEM_DEVICE");
     }
+    /* per-instance launch when this call or the forward call it follows has per-instance times (the kernel reads every
+       time from a [B] array then: a shared one is spread) */
+    const bool pt = tm.on || s->fwd_pt;
+    const double *d_tinits = nullptr;
+    if (pt) {
+        if (!d_t0s && (rc = spread_time(s, s->s_t0, t0, nB, &d_t0s))) return rc;
+        if (!d_tends && (rc = spread_time(s, s->s_tend, tend, nB, &d_tends))) return rc;
+        if (s->fwd_pt) d_tinits = (const double *)s->keep_t0.p;
+        else if ((rc = spread_time(s, s->s_tinit, s->fwd_t0, nB, &d_tinits))) return rc;
+    }
     if (guard_backward_due(s)) {
-        if ((rc = guard_backward(s, B, d_ps, d_pr, rem_stride, t0, tend, d_tv, n_t, d_g, grads_stride))) return rc;
+        Times dtm = tm;
+        dtm.t0s = d_t0s; dtm.tends = d_tends; dtm.on = pt;
+        if ((rc = guard_backward(s, B, d_ps, d_pr, rem_stride, t0, tend, d_tv, n_t, d_g, grads_stride, dtm))) return rc;
     }
     sa_bwd_args a;
     memset(&a, 0, sizeof a);
@@ -753,6 +822,8 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
     a.t0 = t0; a.tend = tend; a.tinitial = s->fwd_t0;
     a.rtolB = s->opt.rtolB; a.atolB = s->opt.atolB; a.rtolQB = s->opt.rtolQB; a.atolQB = s->opt.atolQB;
     a.tvals = d_tv;
+    /* per-instance times (pt: [B] arrays, tinitial = the forward call's t0 of each instance) */
+    a.t0s = d_t0s; a.tends = d_tends; a.tinits = d_tinits; a.tvals_stride = tm.tvals_stride;
     HIP_TRY(hipEventRecord(s->ev[2], s->stream));
     if (!s->tiled) {
         a.B = B; a.traj_cap = s->traj_rows;
@@ -763,7 +834,7 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
         a.traj = (const double *)s->traj.p; a.traj_np = (const int32_t *)s->traj_np.p;
         a.lamda_all = d_lall; a.quad_all = d_qall;
         if ((rc = bind_workspace(s, B, &a.ws, &a.ws_stride))) return rc;
-        if ((rc = launch(s, s->k_backward, B, &a, sizeof a, s->group))) return rc;
+        if ((rc = launch(s, pt ? s->k_backward_t : s->k_backward, B, &a, sizeof a, s->group))) return rc;
     } else {
         /* tiled: re-integrate the forward problem tile by tile with exactly sized storage, adjoint per tile */
         const size_t rec = record_bytes(s), budget = s->budget;      /* the forward call's (not re-evaluated) */
@@ -829,8 +900,10 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
             if ((rc = s->t_np.ensure(sizeof(int32_t) * (size_t)stride))) return rc;
             FwdLaunch f{SA_MODE_ADJ_FWD, tB, s->fwd_n_t, rem_stride, (int32_t)rows, stride, s->fwd_t0,
                         (const double *)s->keep_y0.p + (size_t)lo * nn, d_ps + (size_t)lo * np_,
-                        d_pr + (size_t)lo * (size_t)rem_stride, (const double *)s->keep_tvals.p,
-                        (double *)s->t_yout.p, (int32_t *)s->t_status.p, (int64_t *)s->t_stats.p, (int32_t *)s->t_np.p};
+                        d_pr + (size_t)lo * (size_t)rem_stride,
+                        (const double *)s->keep_tvals.p + (size_t)lo * (size_t)s->fwd_tvals_stride,
+                        (double *)s->t_yout.p, (int32_t *)s->t_status.p, (int64_t *)s->t_stats.p, (int32_t *)s->t_np.p,
+                        s->fwd_pt ? d_tinits + lo : nullptr, s->fwd_tvals_stride, s->fwd_pt};
             if ((rc = launch_forward(s, f))) return rc;
             a.B = tB; a.traj_cap = (int32_t)rows;
             if (!s->point_major) { a.traj_istride = (int32_t)rows; a.traj_stride = 1; }
@@ -843,8 +916,12 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
             a.traj = (const double *)s->traj.p; a.traj_np = (const int32_t *)s->t_np.p;
             a.lamda_all = d_lall ? d_lall + (size_t)lo * (size_t)n_t * nn : nullptr;
             a.quad_all = d_qall ? d_qall + (size_t)lo * (size_t)n_t * np_ : nullptr;
+            a.tvals = d_tv + (size_t)lo * (size_t)tm.tvals_stride;
+            a.t0s = d_t0s ? d_t0s + lo : nullptr;
+            a.tends = d_tends ? d_tends + lo : nullptr;
+            a.tinits = d_tinits ? d_tinits + lo : nullptr;
             if ((rc = bind_workspace(s, tB, &a.ws, &a.ws_stride))) return rc;
-            if ((rc = launch(s, s->k_backward, tB, &a, sizeof a, s->group))) return rc;
+            if ((rc = launch(s, pt ? s->k_backward_t : s->k_backward, tB, &a, sizeof a, s->group))) return rc;
             s->stat_tiles++;
             if ((int64_t)((size_t)rows * stride * rec) > s->stat_arena_bytes) s->stat_arena_bytes = (int64_t)((size_t)rows * stride * rec);
             lo = hi;
@@ -857,6 +934,7 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
         for (int32_t i : s->full_idx)
             HIP_TRY(hipMemcpyAsync(d_status + i, &full, sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
     }
+    if (s->guard && (rc = guard_backward_self_check(s, SA_MEM_DEVICE, d_gout, d_lout, d_status))) return rc;
     if (mem == SA_MEM_HOST) {
         HIP_TRY(hipMemcpyAsync(grad_out, d_gout, sizeof(double) * nB * s->p, hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipMemcpyAsync(lamda_out, d_lout, sizeof(double) * nB * s->n, hipMemcpyDeviceToHost, s->stream));
@@ -870,6 +948,115 @@ extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, con
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     return SA_OK;
+}
+
+extern "C" int sa_solve_backward_batch(sa_solver *s, int mem, int32_t B, const double *ps, const double *pr,
+                                       int32_t rem_stride, double t0, double tend, const double *tvals,
+                                       int32_t n_t, const double *grads, int64_t grads_stride, double *grad_out,
+                                       double *lamda_out, int32_t *status, int64_t *stats)
+{
+    return backward_common(s, mem, B, ps, pr, rem_stride, t0, tend, tvals, n_t, grads, grads_stride, grad_out,
+                           lamda_out, nullptr, nullptr, status, stats, Times());
+}
+
+extern "C" int sa_solve_backward_batch_all(sa_solver *s, int mem, int32_t B, const double *ps, const double *pr,
+                                           int32_t rem_stride, double t0, double tend, const double *tvals,
+                                           int32_t n_t, const double *grads, int64_t grads_stride,
+                                           double *grad_out, double *lamda_out, double *lamda_all_out,
+                                           double *quad_all_out, int32_t *status, int64_t *stats)
+{
+    return backward_common(s, mem, B, ps, pr, rem_stride, t0, tend, tvals, n_t, grads, grads_stride, grad_out,
+                           lamda_out, lamda_all_out, quad_all_out, status, stats, Times());
+}
+
+/* ---- per-instance times (include/sunode_amd.h, sa_*_batch_times) ----
+ * Shape checks, then the plain internals with a Times block.  A time argument with stride 0 becomes the scalar the
+ * plain entry points take (a device-memory one is read back first: that synchronises the handle's stream), so the
+ * kernels see either a scalar or a [B] array. */
+static int time_arg(sa_solver *s, int mem, const double *t, int32_t stride, const char *name, double *scalar,
+                    const double **per_instance)
+{
+    if (!t) return fail(SA_ERR_ARG, "null %s", name);
+    if (stride != 0 && stride != 1) return fail(SA_ERR_ARG, "%s_stride must be 0 or 1", name);
+    *scalar = 0.0;
+    *per_instance = nullptr;
+    if (stride == 1) { *per_instance = t; return SA_OK; }
+    if (mem == SA_MEM_HOST) { *scalar = *t; return SA_OK; }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpyAsync(scalar, t, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return SA_OK;
+}
+
+static int times_args(sa_solver *s, int mem, int32_t n_t, const double *t0, int32_t t0_stride, const double *tend,
+                      int32_t tend_stride, bool want_tend, const double *tvals, int64_t tvals_stride, double *t0_scalar,
+                      double *tend_scalar, Times *tm)
+{
+    if (!s) return fail(SA_ERR_ARG, "null solver");
+    if (mem != SA_MEM_HOST && mem != SA_MEM_DEVICE) return fail(SA_ERR_ARG, "mem must be SA_MEM_HOST or SA_MEM_DEVICE");
+    if (!tvals) return fail(SA_ERR_ARG, "null tvals");
+    if (tvals_stride != 0 && tvals_stride != (int64_t)n_t) return fail(SA_ERR_ARG, "tvals_stride must be 0 or n_t");
+    *tm = Times();
+    tm->on = true;
+    tm->tvals_stride = (int32_t)tvals_stride;
+    int rc = time_arg(s, mem, t0, t0_stride, "t0", t0_scalar, &tm->t0s);
+    if (rc) return rc;
+    *tend_scalar = 0.0;
+    return want_tend ? time_arg(s, mem, tend, tend_stride, "tend", tend_scalar, &tm->tends) : SA_OK;
+}
+
+extern "C" int sa_solve_batch_times(sa_solver *s, int mem, int32_t B, const double *y0, const double *ps,
+                                    const double *pr, int32_t rem_stride, const double *t0, int32_t t0_stride,
+                                    const double *tvals, int64_t tvals_stride, int32_t n_t, double *y_out,
+                                    int32_t *status, int64_t *stats)
+{
+    double t0v, tendv;
+    Times tm;
+    int rc = times_args(s, mem, n_t, t0, t0_stride, nullptr, 0, false, tvals, tvals_stride, &t0v, &tendv, &tm);
+    if (rc) return rc;
+    return forward_common(s, SA_MODE_PLAIN, mem, B, y0, ps, pr, rem_stride, t0v, tvals, n_t, y_out, status, stats, tm);
+}
+
+extern "C" int sa_solve_forward_batch_times(sa_solver *s, int mem, int32_t B, const double *y0, const double *ps,
+                                            const double *pr, int32_t rem_stride, const double *t0, int32_t t0_stride,
+                                            const double *tvals, int64_t tvals_stride, int32_t n_t, double *y_out,
+                                            int32_t *status, int64_t *stats)
+{
+    double t0v, tendv;
+    Times tm;
+    int rc = times_args(s, mem, n_t, t0, t0_stride, nullptr, 0, false, tvals, tvals_stride, &t0v, &tendv, &tm);
+    if (rc) return rc;
+    return forward_common(s, SA_MODE_ADJ_FWD, mem, B, y0, ps, pr, rem_stride, t0v, tvals, n_t, y_out, status, stats, tm);
+}
+
+extern "C" int sa_solve_sens_batch_times(sa_solver *s, int mem, int ism, const double *scaling, int32_t B,
+                                         const double *y0, const double *ps, const double *pr, int32_t rem_stride,
+                                         const double *sens0, const double *t0, int32_t t0_stride,
+                                         const double *tvals, int64_t tvals_stride, int32_t n_t, double *y_out,
+                                         double *sens_out, int32_t *status, int64_t *stats)
+{
+    double t0v, tendv;
+    Times tm;
+    int rc = times_args(s, mem, n_t, t0, t0_stride, nullptr, 0, false, tvals, tvals_stride, &t0v, &tendv, &tm);
+    if (rc) return rc;
+    return sens_common(s, mem, ism, scaling, B, y0, ps, pr, rem_stride, sens0, t0v, tvals, n_t, y_out, sens_out,
+                       status, stats, tm);
+}
+
+extern "C" int sa_solve_backward_batch_times(sa_solver *s, int mem, int32_t B, const double *ps, const double *pr,
+                                             int32_t rem_stride, const double *t0, int32_t t0_stride,
+                                             const double *tend, int32_t tend_stride, const double *tvals,
+                                             int64_t tvals_stride, int32_t n_t, const double *grads,
+                                             int64_t grads_stride, double *grad_out, double *lamda_out,
+                                             double *lamda_all_out, double *quad_all_out, int32_t *status,
+                                             int64_t *stats)
+{
+    double t0v, tendv;
+    Times tm;
+    int rc = times_args(s, mem, n_t, t0, t0_stride, tend, tend_stride, true, tvals, tvals_stride, &t0v, &tendv, &tm);
+    if (rc) return rc;
+    return backward_common(s, mem, B, ps, pr, rem_stride, t0v, tendv, tvals, n_t, grads, grads_stride, grad_out,
+                           lamda_out, lamda_all_out, quad_all_out, status, stats, tm);
 }
 
 
@@ -906,12 +1093,16 @@ struct Guard {
     bool wait_backward = false;    /* ... after two of them: no further forward check until a backward call was seen */
     std::vector<int32_t> idx;      /* the sample of the batch under check (ascending instance indices) */
     bool prefix = true;            /* idx == 0..k-1: the caller's arrays are used in place */
-    DevBuf in[5];                  /* gathered rows of the sample: y0, ps, pr, sens0, grads */
+    DevBuf in[10];                 /* gathered rows of the sample: y0, ps, pr, sens0, grads; per-instance times:
+                                      forward t0 / grid rows, backward t0 / tend / grid rows */
     GuardSeen seen[3];
     int32_t recheck_left[3] = {1, 1, 1}, window[3] = {0, 0, 0};
     std::vector<int32_t> h_status;
     std::vector<int64_t> h_stats;
     DevBuf out[2][4];
+    DevBuf mine;                   /* the main launch's own rows of the sample (guard_self_check) */
+    std::vector<unsigned char> bwd_rows;   /* the default shadow's backward rows of the sample, checked after the main launch */
+    int32_t bwd_k = 0;
     std::vector<unsigned char> host[2];
     std::string detail;
 };
@@ -993,6 +1184,9 @@ static void guard_switch(sa_solver *s)
     std::swap(s->k_eval, g->safe->k_eval);
     std::swap(s->k_math, g->safe->k_math);
     std::swap(s->k_sens, g->safe->k_sens);
+    std::swap(s->k_forward_t, g->safe->k_forward_t);
+    std::swap(s->k_backward_t, g->safe->k_backward_t);
+    std::swap(s->k_sens_t, g->safe->k_sens_t);
     std::swap(s->path, g->safe->path);
     g->using_safe = true;
     g->just_switched = true;
@@ -1208,9 +1402,33 @@ static bool guard_recheck_due(sa_solver *s, uint32_t kind, int32_t B, const int3
 }
 
 /* after the main forward launch of a batch of `mode`: its sample through both shadows */
+/* The default shadow runs the code object of the main launch on the sample's gathered rows (y0, parameters, times):
+   its results must be the main launch's rows of the same instances, bit for bit.  Anything else means the sample was
+   not gathered from the batch's rows -- the comparison with the conservative build would then prove nothing. */
+static int guard_self_check(sa_solver *s, const char *what, int32_t k, const void *d_main, size_t row_bytes,
+                            const DevBuf &shadow_out)
+{
+    Guard *g = s->guard;
+    if (!d_main || !row_bytes || k <= 0) return SA_OK;
+    const void *rows;
+    int rc;
+    if (g->prefix) rows = d_main;
+    else if ((rc = guard_gather(s, g->mine, d_main, row_bytes, true, &rows))) return rc;
+    std::vector<unsigned char> a(row_bytes * (size_t)k), b(row_bytes * (size_t)k);
+    HIP_TRY(hipMemcpyAsync(a.data(), rows, a.size(), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpyAsync(b.data(), shadow_out.p, b.size(), hipMemcpyDeviceToHost, g->fast->stream));
+    HIP_TRY(hipStreamSynchronize(g->fast->stream));
+    for (int32_t i = 0; i < k; i++)
+        if (memcmp(a.data() + (size_t)i * row_bytes, b.data() + (size_t)i * row_bytes, row_bytes) != 0)
+            return fail(SA_ERR_INTERNAL, "guard (%s): the default build's result for sample instance %d is not the batch's "
+                        "own -- the sample's inputs were not gathered from that instance", what, g->idx[(size_t)i]);
+    return SA_OK;
+}
+
 static int guard_forward(sa_solver *s, int mode, int32_t B, const double *d_y0, const double *d_ps, const double *d_pr,
                          int32_t rem_stride, double t0, const double *d_tv, int32_t n_t, const int32_t *d_status,
-                         const int64_t *d_stats)
+                         const int64_t *d_stats, const Times &tm, const double *d_yout)
 {
     Guard *g = s->guard;
     if (mode != SA_MODE_PLAIN) {
@@ -1230,6 +1448,11 @@ static int guard_forward(sa_solver *s, int mode, int32_t B, const double *d_y0, 
     if ((rc = guard_gather(s, g->in[0], d_y0, sizeof(double) * (size_t)s->n, true, &in_y0))) return rc;
     if ((rc = guard_gather(s, g->in[1], d_ps, sizeof(double) * (size_t)s->p, true, &in_ps))) return rc;
     if ((rc = guard_gather(s, g->in[2], d_pr, sizeof(double) * (size_t)s->r, rem_stride != 0, &in_pr))) return rc;
+    Times stm = tm;           /* the sample's own start times and grid rows */
+    const void *in_t0s, *in_tv;
+    if ((rc = guard_gather(s, g->in[5], tm.t0s, sizeof(double), true, &in_t0s))) return rc;
+    if ((rc = guard_gather(s, g->in[6], d_tv, sizeof(double) * (size_t)n_t, tm.tvals_stride != 0, &in_tv))) return rc;
+    stm.t0s = (const double *)in_t0s;
     HIP_TRY(hipStreamSynchronize(s->stream));
     const GuardBuf bufs[3] = {{"y_out", sizeof(double) * (size_t)n_t * nn, sizeof(double) * (size_t)n_t * (size_t)s->n},
                               {"status", sizeof(int32_t), sizeof(int32_t)},
@@ -1239,13 +1462,16 @@ static int guard_forward(sa_solver *s, int mode, int32_t B, const double *d_y0, 
         for (int b = 0; b < 3; b++)
             if ((rc = g->out[w][b].ensure(bufs[b].row_bytes * (size_t)k))) return rc;
         if ((rc = forward_common(sh[w], mode, SA_MEM_DEVICE, k, (const double *)in_y0, (const double *)in_ps,
-                                 (const double *)in_pr, rem_stride, t0, d_tv, n_t,
-                                 (double *)g->out[w][0].p, (int32_t *)g->out[w][1].p, (int64_t *)g->out[w][2].p)))
+                                 (const double *)in_pr, rem_stride, t0, (const double *)in_tv, n_t,
+                                 (double *)g->out[w][0].p, (int32_t *)g->out[w][1].p, (int64_t *)g->out[w][2].p, stm)))
             return rc;
     }
     bool same = true;
     if ((rc = guard_compare(s, mode == SA_MODE_PLAIN ? "forward solve" : "adjoint solve, forward pass", k, bufs, 3, &same)))
         return rc;
+    if (same && (rc = guard_self_check(s, "forward", k, d_yout, sizeof(double) * (size_t)n_t * (size_t)s->n, g->out[0][0])))
+        return rc;
+    if (same && (rc = guard_self_check(s, "forward", k, d_status, sizeof(int32_t), g->out[0][1]))) return rc;
     if (same && (rc = guard_remember(s, mode == SA_MODE_PLAIN ? SA_GUARD_PLAIN : SA_GUARD_ADJOINT, k, 1, 2))) return rc;
     if (mode == SA_MODE_PLAIN) guard_book(s, SA_GUARD_PLAIN, k, same);
     else if (!same) guard_book(s, SA_GUARD_ADJOINT, k, false);
@@ -1255,7 +1481,7 @@ static int guard_forward(sa_solver *s, int mode, int32_t B, const double *d_y0, 
 
 static int guard_sens(sa_solver *s, int ism, const double *scaling, int32_t B, const double *d_y0, const double *d_ps,
                       const double *d_pr, int32_t rem_stride, const double *d_s0, double t0, const double *d_tv,
-                      int32_t n_t, const int32_t *d_status, const int64_t *d_stats)
+                      int32_t n_t, const int32_t *d_status, const int64_t *d_stats, const Times &tm, const double *d_yout)
 {
     Guard *g = s->guard;
     int rc;
@@ -1268,6 +1494,11 @@ static int guard_sens(sa_solver *s, int ism, const double *scaling, int32_t B, c
     if ((rc = guard_gather(s, g->in[1], d_ps, sizeof(double) * (size_t)s->p, true, &in_ps))) return rc;
     if ((rc = guard_gather(s, g->in[2], d_pr, sizeof(double) * (size_t)s->r, rem_stride != 0, &in_pr))) return rc;
     if ((rc = guard_gather(s, g->in[3], d_s0, sizeof(double) * np_n, true, &in_s0))) return rc;
+    Times stm = tm;
+    const void *in_t0s, *in_tv;
+    if ((rc = guard_gather(s, g->in[5], tm.t0s, sizeof(double), true, &in_t0s))) return rc;
+    if ((rc = guard_gather(s, g->in[6], d_tv, sizeof(double) * (size_t)n_t, tm.tvals_stride != 0, &in_tv))) return rc;
+    stm.t0s = (const double *)in_t0s;
     HIP_TRY(hipStreamSynchronize(s->stream));
     const GuardBuf bufs[4] = {{"y_out", sizeof(double) * (size_t)n_t * nn, sizeof(double) * (size_t)n_t * (size_t)s->n},
                               {"sens_out", sizeof(double) * (size_t)n_t * (np_n ? np_n : 1), sizeof(double) * (size_t)n_t * np_n},
@@ -1277,14 +1508,18 @@ static int guard_sens(sa_solver *s, int ism, const double *scaling, int32_t B, c
     for (int w = 0; w < 2; w++) {
         for (int b = 0; b < 4; b++)
             if ((rc = g->out[w][b].ensure(bufs[b].row_bytes * (size_t)k))) return rc;
-        if ((rc = sa_solve_sens_batch(sh[w], SA_MEM_DEVICE, ism, scaling, k, (const double *)in_y0, (const double *)in_ps,
-                                      (const double *)in_pr, rem_stride, (const double *)in_s0, t0, d_tv,
-                                      n_t, (double *)g->out[w][0].p, (double *)g->out[w][1].p, (int32_t *)g->out[w][2].p,
-                                      (int64_t *)g->out[w][3].p)))
+        if ((rc = sens_common(sh[w], SA_MEM_DEVICE, ism, scaling, k, (const double *)in_y0, (const double *)in_ps,
+                              (const double *)in_pr, rem_stride, (const double *)in_s0, t0, (const double *)in_tv,
+                              n_t, (double *)g->out[w][0].p, (double *)g->out[w][1].p, (int32_t *)g->out[w][2].p,
+                              (int64_t *)g->out[w][3].p, stm)))
             return rc;
     }
     bool same = true;
     if ((rc = guard_compare(s, "forward-sensitivity solve", k, bufs, 4, &same))) return rc;
+    if (same && (rc = guard_self_check(s, "sensitivities", k, d_yout, sizeof(double) * (size_t)n_t * (size_t)s->n,
+                                       g->out[0][0])))
+        return rc;
+    if (same && (rc = guard_self_check(s, "sensitivities", k, d_status, sizeof(int32_t), g->out[0][2]))) return rc;
     if (same && (rc = guard_remember(s, SA_GUARD_SENS, k, 2, 3))) return rc;
     guard_book(s, SA_GUARD_SENS, k, same);
     return SA_OK;
@@ -1292,7 +1527,7 @@ static int guard_sens(sa_solver *s, int ism, const double *scaling, int32_t B, c
 
 static int guard_backward(sa_solver *s, int32_t B, const double *d_ps, const double *d_pr, int32_t rem_stride,
                           double t0, double tend, const double *d_tv, int32_t n_t, const double *d_g,
-                          int64_t grads_stride)
+                          int64_t grads_stride, const Times &tm)
 {
     Guard *g = s->guard;
     if (g->wait_backward) { g->wait_backward = false; g->fwd_only = 0; }       /* the next forward call checks again */
@@ -1305,6 +1540,13 @@ static int guard_backward(sa_solver *s, int32_t B, const double *d_ps, const dou
     const void *in_pr = (g->prefix || rem_stride == 0) ? (const void *)d_pr : g->in[2].p;
     const void *in_g;
     if ((rc = guard_gather(s, g->in[4], d_g, sizeof(double) * (size_t)n_t * (size_t)s->n, grads_stride != 0, &in_g))) return rc;
+    Times stm = tm;           /* the sample's own final / initial times and grid rows */
+    const void *in_t0s, *in_tends, *in_tv;
+    if ((rc = guard_gather(s, g->in[7], tm.t0s, sizeof(double), true, &in_t0s))) return rc;
+    if ((rc = guard_gather(s, g->in[8], tm.tends, sizeof(double), true, &in_tends))) return rc;
+    if ((rc = guard_gather(s, g->in[9], d_tv, sizeof(double) * (size_t)n_t, tm.tvals_stride != 0, &in_tv))) return rc;
+    stm.t0s = (const double *)in_t0s;
+    stm.tends = (const double *)in_tends;
     HIP_TRY(hipStreamSynchronize(s->stream));
     const GuardBuf bufs[4] = {{"grad_out", sizeof(double) * pp, sizeof(double) * (size_t)s->p},
                               {"lamda_out", sizeof(double) * nn, sizeof(double) * (size_t)s->n},
@@ -1314,14 +1556,31 @@ static int guard_backward(sa_solver *s, int32_t B, const double *d_ps, const dou
     for (int w = 0; w < 2; w++) {
         for (int b = 0; b < 4; b++)
             if ((rc = g->out[w][b].ensure(bufs[b].row_bytes * (size_t)k))) return rc;
-        if ((rc = sa_solve_backward_batch_all(sh[w], SA_MEM_DEVICE, k, (const double *)in_ps, (const double *)in_pr,
-                                              rem_stride, t0, tend, d_tv, n_t, (const double *)in_g,
-                                              grads_stride, (double *)g->out[w][0].p, (double *)g->out[w][1].p, nullptr,
-                                              nullptr, (int32_t *)g->out[w][2].p, (int64_t *)g->out[w][3].p)))
+        if ((rc = backward_common(sh[w], SA_MEM_DEVICE, k, (const double *)in_ps, (const double *)in_pr,
+                                  rem_stride, t0, tend, (const double *)in_tv, n_t, (const double *)in_g,
+                                  grads_stride, (double *)g->out[w][0].p, (double *)g->out[w][1].p, nullptr,
+                                  nullptr, (int32_t *)g->out[w][2].p, (int64_t *)g->out[w][3].p, stm)))
             return rc;
     }
     bool same = true;
     if ((rc = guard_compare(s, "adjoint solve, backward pass", k, bufs, 4, &same))) return rc;
+    g->bwd_k = 0;
+    if (same) {     /* the default shadow's rows, for guard_backward_self_check after the main launch */
+        const size_t rb = sizeof(double) * (size_t)(s->p + s->n) + sizeof(int32_t);
+        g->bwd_rows.resize(rb * (size_t)k);
+        std::vector<double> gp((size_t)k * pp), ln((size_t)k * nn);
+        std::vector<int32_t> st((size_t)k);
+        HIP_TRY(hipMemcpy(gp.data(), g->out[0][0].p, sizeof(double) * gp.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ln.data(), g->out[0][1].p, sizeof(double) * ln.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(st.data(), g->out[0][2].p, sizeof(int32_t) * st.size(), hipMemcpyDeviceToHost));
+        for (int32_t i = 0; i < k; i++) {
+            unsigned char *r = g->bwd_rows.data() + (size_t)i * rb;
+            memcpy(r, gp.data() + (size_t)i * pp, sizeof(double) * (size_t)s->p);
+            memcpy(r + sizeof(double) * (size_t)s->p, ln.data() + (size_t)i * nn, sizeof(double) * (size_t)s->n);
+            memcpy(r + sizeof(double) * (size_t)(s->p + s->n), &st[(size_t)i], sizeof(int32_t));
+        }
+        g->bwd_k = k;
+    }
     g->adj_k = 0;
     g->fwd_only = 0;
     guard_book(s, SA_GUARD_ADJOINT, k, same);
@@ -1335,11 +1594,41 @@ static int guard_backward(sa_solver *s, int32_t B, const double *d_ps, const dou
         if ((rc = s->t_yout.ensure(sizeof(double) * nB * (size_t)s->fwd_n_t * nn))) return rc;
         if ((rc = s->t_status.ensure(sizeof(int32_t) * (size_t)round64(s->fwd_B)))) return rc;
         if ((rc = s->t_stats.ensure(sizeof(int64_t) * (size_t)round64(s->fwd_B) * SA_N_STATS))) return rc;
+        Times ftm;            /* the forward call's times, kept by the handle */
+        ftm.t0s = s->fwd_pt ? (const double *)s->keep_t0.p : nullptr;
+        ftm.on = s->fwd_pt;
+        ftm.tvals_stride = s->fwd_tvals_stride;
         if ((rc = forward_common(s, SA_MODE_ADJ_FWD, SA_MEM_DEVICE, s->fwd_B, (const double *)s->keep_y0.p, d_ps, d_pr,
                                  rem_stride, s->fwd_t0, (const double *)s->keep_tvals.p, s->fwd_n_t,
-                                 (double *)s->t_yout.p, (int32_t *)s->t_status.p, (int64_t *)s->t_stats.p)))
+                                 (double *)s->t_yout.p, (int32_t *)s->t_status.p, (int64_t *)s->t_stats.p, ftm)))
             return rc;
         if ((rc = resolve_forward(s))) return rc;
+    }
+    return SA_OK;
+}
+
+/* after the main backward launch: its rows of the sample must be the default shadow's (see guard_self_check) */
+static int guard_backward_self_check(sa_solver *s, int mem, const double *grad_out, const double *lamda_out,
+                                     const int32_t *status)
+{
+    Guard *g = s->guard;
+    const int32_t k = g->bwd_k;
+    g->bwd_k = 0;
+    if (mem != SA_MEM_DEVICE || k != (int32_t)g->idx.size()) return SA_OK;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t pb = sizeof(double) * (size_t)s->p, nb = sizeof(double) * (size_t)s->n;
+    std::vector<unsigned char> row(pb + nb + sizeof(int32_t));
+    for (int32_t i = 0; i < k; i++) {
+        const size_t j = (size_t)g->idx[(size_t)i];
+        if (pb) HIP_TRY(hipMemcpy(row.data(), grad_out + j * (size_t)s->p, pb, hipMemcpyDeviceToHost));
+        if (nb) HIP_TRY(hipMemcpy(row.data() + pb, lamda_out + j * (size_t)s->n, nb, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(row.data() + pb + nb, status + j, sizeof(int32_t), hipMemcpyDeviceToHost));
+        int32_t st;
+        memcpy(&st, row.data() + pb + nb, sizeof st);
+        if (st == SA_STATUS_ARENA_FULL) continue;      /* (decided for the whole batch's arena, not the sample's) */
+        if (memcmp(row.data(), g->bwd_rows.data() + (size_t)i * row.size(), row.size()) != 0)
+            return fail(SA_ERR_INTERNAL, "guard (backward): the default build's result for sample instance %zu is not "
+                        "the batch's own -- the sample's inputs were not gathered from that instance", j);
     }
     return SA_OK;
 }

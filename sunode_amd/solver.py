@@ -387,6 +387,58 @@ class _EngineMixin:
             pr = np.zeros(1)
         return B, y0, ps, pr, stride
 
+    # -- time arguments of the batch methods: shared (a scalar t0 / tend, a 1-d grid [n_t]) or per instance ([B] start
+    #    / end times, a [B, n_t] grid).  All-shared calls take the plain entry points exactly as before; any per-instance
+    #    argument selects the sa_*_batch_times entry points (include/sunode_amd.h), every instance then being solved as
+    #    if alone with its own times.  Checked here, before any device work.
+    @staticmethod
+    def _host_times(x) -> np.ndarray:
+        if _is_device_tensor(x):
+            x = x.detach().cpu().numpy()
+        x = np.asarray(x, dtype=np.float64)
+        return x if x.ndim == 0 else np.ascontiguousarray(x)       # (ascontiguousarray makes a scalar 1-d)
+
+    def _time_args(self, B, t0, tvals, tend=None, has_tend=False):
+        """(t0, t0_stride, tend, tend_stride, tvals, n_t, tvals_stride, per_instance): strides None for shared
+        values (t0 / tend then Python floats, tvals the 1-d grid); per-instance arrays in the caller's order
+        (``_gather`` puts them in handle order once the batch's handles are active)."""
+        tvals = self._host_times(tvals)
+        if tvals.ndim == 0:             # a single output time, as np.ascontiguousarray has always read it
+            tvals = tvals.reshape(1)
+        if tvals.ndim not in (1, 2):
+            raise ValueError("tvals must have shape (n_t,) or (B, n_t), not %s" % (tvals.shape,))
+        times = [(t0, "t0")] + ([(tend, "tend")] if has_tend else [])
+        arrays = [self._host_times(t) for t, _ in times]
+        for a, (_, name) in zip(arrays, times):
+            if a.ndim > 1:
+                raise ValueError("%s must be a scalar or have shape (B,), not %s" % (name, a.shape))
+        per_instance = tvals.ndim == 2 or any(a.ndim == 1 for a in arrays)
+        n_t = tvals.shape[-1]
+        if not per_instance:
+            out = [float(a) for a in arrays]
+            return out[0], None, (out[1] if has_tend else None), None, tvals, n_t, None, False
+        if B is None:
+            raise ValueError("y0 must have shape (B, n_states)")
+        if tvals.ndim == 2 and tvals.shape[0] != B:
+            raise ValueError("tvals of shape %s: a per-instance grid must have shape (B, n_t) = (%d, n_t)"
+                             % (tvals.shape, B))
+        if n_t == 0:
+            raise ValueError("per-instance time grids need at least one output time")
+        res = []
+        for a, (_, name) in zip(arrays, times):
+            if a.ndim == 1 and a.shape != (B,):
+                raise ValueError("%s of shape %s: per-instance times must have shape (B,) = (%d,)" % (name, a.shape, B))
+            res.append((a, 1) if a.ndim == 1 else (float(a), None))
+        tv_stride = n_t if tvals.ndim == 2 else None
+        t0v, t0s = res[0]
+        tev, tes = res[1] if has_tend else (None, None)
+        return t0v, t0s, tev, tes, tvals, n_t, tv_stride, True
+
+    @staticmethod
+    def _time_rows(x, stride, lo, hi):
+        """Instances [lo, hi) of a time argument (shared ones whole)."""
+        return x[lo:hi] if stride is not None else x
+
     @staticmethod
     def stats_as_dict(stats: np.ndarray) -> Dict[str, np.ndarray]:
         return {name: stats[..., i] for i, name in enumerate(_native.STAT_NAMES[:15])}
@@ -529,15 +581,18 @@ class Solver(_EngineMixin):
         ``out``: caller-allocated outputs (see ``solve_batch``), names ``y_out, sens_out, status, stats``."""
         if not self._compute_sens:
             raise ValueError("construct the Solver with sens_mode='simultaneous' or 'staggered'")
+        t0, t0_st, _, _, tvals, n_t, tv_st, per = self._time_args(np.shape(y0)[0] if np.ndim(y0) == 2 else None,
+                                                                 t0, tvals)
+        tk = dict(t0_stride=t0_st, tvals_stride=tv_st) if per else {}       # (shared: the plain entry points)
         self._set_retries(max_retries_fwd=max_retries)
         B, y0, ps, pr, stride = self._batch_inputs(y0, params_sub, params_rem)
         n, p = self._problem.n_states, self._problem.n_params
         sens0 = np.ascontiguousarray(np.broadcast_to(np.asarray(sens0, dtype=np.float64), (B, p, n)))
-        tvals = np.ascontiguousarray(tvals, dtype=np.float64)
         y0, ps, pr, sens0 = self._gather(y0), self._gather(ps, p), self._gather(pr, stride), self._gather(sens0)
+        t0, tvals = self._gather(t0, t0_st), self._gather(tvals, tv_st)
         names = ("y_out", "sens_out", "status", "stats")
-        y_pair = self._out("sens.y_out", (B, len(tvals), n), given=self._out_arg(out, 0, names))
-        s_pair = self._out("sens.sens_out", (B, len(tvals), p, n), given=self._out_arg(out, 1, names))
+        y_pair = self._out("sens.y_out", (B, n_t, n), given=self._out_arg(out, 0, names))
+        s_pair = self._out("sens.sens_out", (B, n_t, p, n), given=self._out_arg(out, 1, names))
         st_pair = self._out("sens.status", (B,), np.int32, self._out_arg(out, 2, names), small=True)
         sa_pair = self._out("sens.stats", (B, _native.N_STATS), np.int64, self._out_arg(out, 3, names), small=True)
         y_out, sens_out, status, stats = y_pair[0], s_pair[0], st_pair[0], sa_pair[0]
@@ -546,8 +601,9 @@ class Solver(_EngineMixin):
         def call(eng, lo, hi):
             eng.solve_sens(_native.SA_MEM_HOST, ism, self._scaling_factors, hi - lo, y0[lo:hi],
                            _rows(ps, lo, hi, p), _rows(pr, lo, hi, stride), stride,
-                           sens0[lo:hi] if sens0.size else np.zeros(1), t0, tvals, len(tvals), y_out[lo:hi],
-                           sens_out[lo:hi] if sens_out.size else np.zeros(1), status[lo:hi], stats[lo:hi])
+                           sens0[lo:hi] if sens0.size else np.zeros(1), self._time_rows(t0, t0_st, lo, hi),
+                           self._time_rows(tvals, tv_st, lo, hi), n_t, y_out[lo:hi],
+                           sens_out[lo:hi] if sens_out.size else np.zeros(1), status[lo:hi], stats[lo:hi], **tk)
         self._run_shards(self._shards(B), call)
         return self._scatter(y_pair), self._scatter(s_pair), self._scatter(st_pair), self._scatter(sa_pair)
 
@@ -559,21 +615,25 @@ class Solver(_EngineMixin):
         (``solve(t0, tvals, y0, y_out)``, /root/reference/sunode/solver.py:467) carried over to the batch: a dict
         ``{"y_out": ..., "status": ..., "stats": ...}`` or a sequence in return order, entries may be missing / None.
         Arrays must be C-contiguous float64 (status int32, stats int64) of the exact shape."""
+        t0, t0_st, _, _, tvals, n_t, tv_st, per = self._time_args(np.shape(y0)[0] if np.ndim(y0) == 2 else None,
+                                                                 t0, tvals)
+        tk = dict(t0_stride=t0_st, tvals_stride=tv_st) if per else {}       # (shared: the plain entry points)
         self._select_mapping(np.shape(y0)[0] if np.ndim(y0) == 2 else 0)
         self._set_retries(max_retries_fwd=max_retries)
         B, y0, ps, pr, stride = self._batch_inputs(y0, params_sub, params_rem)
-        tvals = np.ascontiguousarray(tvals, dtype=np.float64)
         p = self._problem.n_params
         y0, ps, pr = self._gather(y0), self._gather(ps, p), self._gather(pr, stride)
+        t0, tvals = self._gather(t0, t0_st), self._gather(tvals, tv_st)
         names = ("y_out", "status", "stats")
-        y_pair = self._out("solve.y_out", (B, len(tvals), self._problem.n_states), given=self._out_arg(out, 0, names))
+        y_pair = self._out("solve.y_out", (B, n_t, self._problem.n_states), given=self._out_arg(out, 0, names))
         st_pair = self._out("solve.status", (B,), np.int32, self._out_arg(out, 1, names), small=True)
         sa_pair = self._out("solve.stats", (B, _native.N_STATS), np.int64, self._out_arg(out, 2, names), small=True)
         y_out, status, stats = y_pair[0], st_pair[0], sa_pair[0]
 
         def call(eng, lo, hi):
             eng.solve(_native.SA_MEM_HOST, hi - lo, y0[lo:hi], _rows(ps, lo, hi, p), _rows(pr, lo, hi, stride),
-                      stride, t0, tvals, len(tvals), y_out[lo:hi], status[lo:hi], stats[lo:hi])
+                      stride, self._time_rows(t0, t0_st, lo, hi), self._time_rows(tvals, tv_st, lo, hi), n_t,
+                      y_out[lo:hi], status[lo:hi], stats[lo:hi], **tk)
         self._run_shards(self._shards(B), call)
         return self._scatter(y_pair), self._scatter(st_pair), self._scatter(sa_pair)
 
@@ -713,14 +773,17 @@ class AdjointSolver(_EngineMixin):
         ``out``: caller-allocated outputs written in place (the reference's convention,
         /root/reference/sunode/solver.py:682: ``solve_forward(t0, tvals, y0, y_out)``): a dict with some of
         ``y_out, status, stats`` or a sequence in return order; see ``Solver.solve_batch``."""
+        t0, t0_st, _, _, tvals, n_t, tv_st, per = self._time_args(np.shape(y0)[0] if np.ndim(y0) == 2 else None,
+                                                                 t0, tvals)
+        tk = dict(t0_stride=t0_st, tvals_stride=tv_st) if per else {}       # (shared: the plain entry points)
         self._select_mapping(np.shape(y0)[0] if np.ndim(y0) == 2 else 0)
         self._set_retries(max_retries_fwd=max_retries)
         B, y0, ps, pr, stride = self._batch_inputs(y0, params_sub, params_rem)
-        tvals = np.ascontiguousarray(tvals, dtype=np.float64)
         p = self._problem.n_params
         y0, ps, pr = self._gather(y0), self._gather(ps, p), self._gather(pr, stride)
+        t0, tvals = self._gather(t0, t0_st), self._gather(tvals, tv_st)
         names = ("y_out", "status", "stats")
-        y_pair = self._out("fwd.y_out", (B, len(tvals), self._problem.n_states), given=self._out_arg(out, 0, names))
+        y_pair = self._out("fwd.y_out", (B, n_t, self._problem.n_states), given=self._out_arg(out, 0, names))
         st_pair = self._out("fwd.status", (B,), np.int32, self._out_arg(out, 1, names), small=True)
         sa_pair = self._out("fwd.stats", (B, _native.N_STATS), np.int64, self._out_arg(out, 2, names), small=True)
         y_out, status, stats = y_pair[0], st_pair[0], sa_pair[0]
@@ -728,7 +791,8 @@ class AdjointSolver(_EngineMixin):
 
         def call(eng, lo, hi):
             eng.solve(_native.SA_MEM_HOST, hi - lo, y0[lo:hi], _rows(ps, lo, hi, p), _rows(pr, lo, hi, stride),
-                      stride, t0, tvals, len(tvals), y_out[lo:hi], status[lo:hi], stats[lo:hi], adjoint=True)
+                      stride, self._time_rows(t0, t0_st, lo, hi), self._time_rows(tvals, tv_st, lo, hi), n_t,
+                      y_out[lo:hi], status[lo:hi], stats[lo:hi], adjoint=True, **tk)
         self._run_shards(shards, call)
         self._last_forward = (B, ps, pr, stride, shards, self._mapping)     # every handle keeps ITS shard's trajectories
         return self._scatter(y_pair), self._scatter(st_pair), self._scatter(sa_pair)
@@ -745,11 +809,12 @@ class AdjointSolver(_EngineMixin):
         status, stats, lamda_all, quad_all`` or a sequence in return order."""
         if self._last_forward is None:
             raise SolverError("solve_backward called before solve_forward")
-        B, ps, pr, stride, shards, self._mapping = self._last_forward      # (the handles that integrated forward)
+        B, ps, pr, stride, shards, mapping = self._last_forward      # (the handles that integrated forward)
+        t0, t0_st, tend, te_st, tvals, n_t, tv_st, per = self._time_args(B, t0, tvals, tend, has_tend=True)
+        tk = dict(t0_stride=t0_st, tend_stride=te_st, tvals_stride=tv_st) if per else {}
+        self._mapping = mapping
         self._set_retries(max_retries_bwd=max_retries)
         n, p = self._problem.n_states, self._problem.n_params
-        tvals = np.ascontiguousarray(tvals, dtype=np.float64)
-        n_t = len(tvals)
         grads = np.ascontiguousarray(grads, dtype=np.float64)
         if grads.shape == (n_t, n):
             gstride = 0
@@ -758,6 +823,7 @@ class AdjointSolver(_EngineMixin):
         else:
             raise ValueError(f"grads must have shape ({n_t}, {n}) or ({B}, {n_t}, {n})")
         grads = self._gather(grads, gstride)                 # (ps / pr of the forward call are in handle order already)
+        t0, tend, tvals = self._gather(t0, t0_st), self._gather(tend, te_st), self._gather(tvals, tv_st)
         names = ("grad_out", "lamda_out", "status", "stats", "lamda_all", "quad_all")
         if out is not None and not return_all and (len(out) > 4 if not isinstance(out, dict)
                                                    else {"lamda_all", "quad_all"} & set(out)):
@@ -780,9 +846,10 @@ class AdjointSolver(_EngineMixin):
 
         def call(eng, lo, hi):
             eng.solve_backward(_native.SA_MEM_HOST, hi - lo, _rows(ps, lo, hi, p), _rows(pr, lo, hi, stride), stride,
-                               t0, tend, tvals, n_t, _rows(grads, lo, hi, gstride), gstride, grad_out[lo:hi],
-                               lamda_out[lo:hi], status[lo:hi], stats[lo:hi],
-                               lam_all[lo:hi] if return_all else None, quad_all[lo:hi] if return_all else None)
+                               self._time_rows(t0, t0_st, lo, hi), self._time_rows(tend, te_st, lo, hi),
+                               self._time_rows(tvals, tv_st, lo, hi), n_t, _rows(grads, lo, hi, gstride), gstride,
+                               grad_out[lo:hi], lamda_out[lo:hi], status[lo:hi], stats[lo:hi],
+                               lam_all[lo:hi] if return_all else None, quad_all[lo:hi] if return_all else None, **tk)
         self._run_shards(shards, call)
         # (p == 0 / n == 0: the caller's (B, 0) array, if any, has nothing to receive)
         grad_out = self._scatter(g_pair) if p else self._zero_width(self._out_arg(out, 0, names), (B, 0))

@@ -5,7 +5,8 @@ Counterpart of /root/reference/sunode/wrappers/as_pytensor.py (``solve_ivp`` ``:
 ``:311-344``) on top of the HIP engine.  Both gradient paths are wired: ``derivatives='adjoint'``
 (``SolveODEAdjoint``) and ``derivatives='forward'`` (``SolveODE``, forward sensitivities, ``:186-264``).
 On top of the reference's per-draw Ops there is a batched pair (``SolveODEAdjointBatch`` / ``...BatchBackward``) whose
-leading axis is the parameter draw, which is what actually feeds a GPU.
+leading axis is the parameter draw, which is what actually feeds a GPU, and its counterpart with a start time and an
+output grid per draw (``SolveODEAdjointBatchTimes`` / ``...BatchTimesBackward`` / ``EvalRhsBatchTimes``).
 
 pytensor is an optional dependency: importing this module without it raises ``ImportError``.
 Gradient wiring (reference ``:294-308``): d/dy0 = -lamda, d/dparams = grad_out,
@@ -268,5 +269,74 @@ class SolveODEAdjointBatchBackward(Op):
         self._solver.solve_forward_batch(float(t0), tvals, y0, params, params_fixed)
         grad_out, lamda_out, _, _ = self._solver.solve_backward_batch(
             float(tvals[-1]), float(t0), tvals, np.ascontiguousarray(grads))
+        outputs[0][0] = lamda_out
+        outputs[1][0] = grad_out
+
+
+# -- per-instance start times and output grids (t0 [B], tvals [B, n_t]: Solver / AdjointSolver batch methods) ----------
+class EvalRhsBatchTimes(Op):
+    """rhs(t_bi, y_bi) on every draw's own grid (d/dtvals of ``SolveODEAdjointBatchTimes``)."""
+    itypes = [pt.dmatrix, pt.dvector, pt.dtensor3, pt.dmatrix]      # params [B,p], params_fixed [r], y [B,n_t,n], tvals [B,n_t]
+    otypes = [pt.dtensor3]
+    __props__ = ("_solver_id",)
+
+    def __init__(self, solver):
+        self._solver = solver
+        self._solver_id = id(solver)
+
+    def perform(self, node, inputs, outputs):
+        params, params_fixed, y, tvals = inputs
+        eng = self._solver._engine()
+        B, n_t, n = y.shape
+        fixed = self._solver._problem.extend_remainder(params_fixed) if len(params_fixed) else params_fixed
+        res = eng.eval_callbacks(np.ascontiguousarray(tvals).reshape(B * n_t), y.reshape(B * n_t, n),
+                                 np.zeros((B * n_t, n)), np.repeat(params, n_t, axis=0), np.tile(fixed, (B * n_t, 1)))
+        if res["codes"][:, 0].any():
+            raise ValueError("Bad ode rhs return code: 1")
+        outputs[0][0] = res["rhs"].reshape(B, n_t, n)
+
+
+class SolveODEAdjointBatchTimes(Op):
+    """``SolveODEAdjointBatch`` with a start time and an output grid per draw: y0 [B,n], params [B,p], params_fixed [r],
+    t0 [B], tvals [B,n_t] -> [B,n_t,n].  Each draw is solved as the per-draw Op would solve it on its own times; the
+    gradient w.r.t. tvals is per draw ([B, n_t], no sum over the batch); t0 is not differentiable."""
+    itypes = [pt.dmatrix, pt.dmatrix, pt.dvector, pt.dvector, pt.dmatrix]
+    otypes = [pt.dtensor3]
+    __props__ = ("_solver_id",)
+
+    def __init__(self, solver):
+        self._solver = solver
+        self._solver_id = id(solver)
+
+    def perform(self, node, inputs, outputs):
+        y0, params, params_fixed, t0, tvals = inputs
+        y, _, _ = self._solver.solve_forward_batch(t0, tvals, y0, params, params_fixed)
+        outputs[0][0] = y
+
+    def grad(self, inputs, g):
+        g, = g
+        y0, params, params_fixed, t0, tvals = inputs
+        solution = self(*inputs)
+        lamda, gradient = SolveODEAdjointBatchTimesBackward(self._solver)(y0, params, params_fixed, g, t0, tvals)
+        d_tvals = (EvalRhsBatchTimes(self._solver)(params, params_fixed, solution, tvals) * g).sum(-1)
+        return [-lamda, gradient, grad_not_implemented(self, 2, params_fixed),
+                grad_not_implemented(self, 3, t0), d_tvals]
+
+
+class SolveODEAdjointBatchTimesBackward(Op):
+    itypes = [pt.dmatrix, pt.dmatrix, pt.dvector, pt.dtensor3, pt.dvector, pt.dmatrix]
+    otypes = [pt.dmatrix, pt.dmatrix]                                 # lamda [B,n], gradient [B,p]
+    __props__ = ("_solver_id",)
+
+    def __init__(self, solver):
+        self._solver = solver
+        self._solver_id = id(solver)
+
+    def perform(self, node, inputs, outputs):
+        y0, params, params_fixed, grads, t0, tvals = inputs
+        tvals = np.ascontiguousarray(tvals)
+        self._solver.solve_forward_batch(t0, tvals, y0, params, params_fixed)
+        grad_out, lamda_out, _, _ = self._solver.solve_backward_batch(
+            np.ascontiguousarray(tvals[:, -1]), t0, tvals, np.ascontiguousarray(grads))
         outputs[0][0] = lamda_out
         outputs[1][0] = grad_out
