@@ -99,3 +99,45 @@ def test_grad_per_draw_and_equal_rows_sum_to_the_shared_op(ops):
     ys, dts, yp, dtp = pytensor.evaluate([shared, gs[4], per, gp[4]], givens)
     np.testing.assert_array_equal(yp, ys)
     np.testing.assert_allclose(dtp.sum(0), dts, rtol=1e-14, atol=0)
+
+
+def _forcing_truth():
+    from tests.test_time_grid_truth import load_truth
+    return load_truth(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"), "forcing")
+
+
+def _forcing_solver():
+    from sunode_amd.solver import AdjointSolver
+    tol = 1e-9
+    return AdjointSolver(make_problem("forcing"), abstol=tol, reltol=tol, backward_abstol=tol, backward_reltol=tol,
+                         quad_abstol=tol, quad_reltol=tol)
+
+
+def _rel_rows(got, want):
+    return np.max(np.abs(got - want) / np.abs(want).max(axis=1, keepdims=True))
+
+
+def test_eval_rhs_reads_each_draws_own_times(ops):
+    """EvalRhsBatchTimes.perform on ``forcing`` (its right-hand side reads t) at the truth's states and per-draw grids:
+    rhs . g equals the fixture's d_tvals (tests/golden/truth_times_forcing.npz) -- a time column in the wrong order or
+    tiled from one row would not."""
+    t = _forcing_truth()
+    rhs, = _run(ops.EvalRhsBatchTimes(_forcing_solver()), [t["ps"], t["pr"], t["y_out"], t["tvals"]], 1)
+    assert rhs.shape == t["y_out"].shape
+    assert _rel_rows((rhs * t["grads"]).sum(-1), t["d_tvals"]) < 1e-5
+
+
+def test_graph_d_tvals_of_a_time_dependent_model_vs_truth(ops):
+    """The graph's d/dtvals of SolveODEAdjointBatchTimes on ``forcing`` with the fixture's per-draw t0 / tvals against
+    the truth's d_tvals = f(t_bk, y_b(t_bk)) . g_bk."""
+    pytensor = pytest.importorskip("pytensor")
+    if not hasattr(pytensor, "evaluate"):
+        pytest.skip("graph evaluation helper of the stub only")
+    pt = importlib.import_module("pytensor.tensor")
+    t = _forcing_truth()
+    y0v, pv = pt.dmatrix("y0"), pt.dmatrix("params")
+    flat = ops.SolveODEAdjointBatchTimes(_forcing_solver())(y0v, pv, t["pr"], t["t0"], t["tvals"])
+    gl = flat.owner.op.grad(flat.owner.inputs, [pt.as_tensor_variable(t["grads"])])
+    d_tvals, = pytensor.evaluate([gl[4]], {y0v: t["y0"], pv: t["ps"]})
+    assert d_tvals.shape == t["d_tvals"].shape
+    assert _rel_rows(d_tvals, t["d_tvals"]) < 1e-5

@@ -14,6 +14,7 @@ Independent oracles for the integrator half:
   wrappers/as_pytensor.py:294-308).
 
 Usage: python tools/make_golden_truth.py   (a few minutes; outputs are committed)
+       python tools/make_golden_truth.py --times    (only truth_times_<name>.npz: see ``times_truth``)
 """
 from __future__ import annotations
 
@@ -30,7 +31,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 from sunode_amd import SympyProblem  # noqa: E402
 from sunode_amd.symode.problem import HOST_FUNCTIONS  # noqa: E402
-from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, forcing_batch, logistic_switch_batch, lv_batch,  # noqa: E402
+from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, forcing_batch, logistic_switch_batch, lv_batch,  # noqa: E402
                             misc_batch, robertson_batch, seir_batch)
 
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -136,8 +137,150 @@ def sweep_truth():
                  tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
 
 
+def plain_rhs(prob):
+    """Callable f(t, y, ps, pr) -> dy/dt of the model alone."""
+    y = list(prob._sym_statevec)
+    f = sym.lambdify([prob._sym_time, y, list(prob._sym_deriv_paramsvec), list(prob._sym_fixed_paramsvec)],
+                     list(prob._sym_dydt), modules=[HOST_FUNCTIONS, "numpy"], cse=True)
+    return lambda t, yv, psv, prv: np.asarray(f(t, yv, psv, prv), dtype=float)
+
+
+def truth_times_batch(prob, y0, ps, pr, t0, tvals, tend, grads, rtol=1e-13, atol=1e-15):
+    """Per-instance times: instance b starts at t0[b], is observed at tvals[b] (non-decreasing, repeats allowed) and its
+    backward pass ends at tend[b] (t0[b] <= tend[b] <= tvals[b, 0]).
+
+    Returns y_out [B, n_t, n]; sens [B, n_t, p, n], the forward sensitivities from t0 with S(t0) =
+    initial_sensitivities(prob); grad_params [B, p] and grad_y_tend [B, n], dL/dp and dL/dy(tend) of
+    L = sum_k g_k . y(t_k) for the system restarted at y(tend) with S = 0, S0 = I (what the backward pass that stops
+    at tend returns as grad_out and -lamda_out); d_tvals [B, n_t] = f(t_k, y(t_k)) . g_k."""
+    from sunode_amd.solver import initial_sensitivities
+    n, p = prob.n_states, prob.n_params
+    B, n_t = tvals.shape
+    sens0 = initial_sensitivities(prob)
+    rhs = augmented_rhs(prob)
+    f = plain_rhs(prob)
+    out = dict(y_out=np.zeros((B, n_t, n)), sens=np.zeros((B, n_t, p, n)), grad_params=np.zeros((B, p)),
+               grad_y_tend=np.zeros((B, n)), d_tvals=np.zeros((B, n_t)))
+
+    def run(ta, times, z0, psb, prb):
+        """z at each of `times` (>= ta) of the augmented system started at (ta, z0)."""
+        te = np.unique(times)
+        if te[-1] == ta:                    # (nothing to integrate: every time is the start)
+            return {ta: z0}
+        sol = solve_ivp(rhs, (ta, te[-1]), z0, method="DOP853", t_eval=te, args=(psb, prb), rtol=rtol, atol=atol)
+        assert sol.success, sol.message
+        return dict(zip(te.tolist(), sol.y.T))
+
+    for b in range(B):
+        prb = pr if pr.ndim == 1 else pr[b]
+        tv, g = tvals[b], grads[b]
+        assert t0[b] <= tend[b] <= tv[0] and (np.diff(tv) >= 0).all()
+        z0 = np.concatenate([y0[b], sens0.ravel(), np.eye(n).ravel()])
+        zs = run(t0[b], np.append(tv, tend[b]), z0, ps[b], prb)
+        z = np.array([zs[t] for t in tv.tolist()])
+        out["y_out"][b] = z[:, :n]
+        out["sens"][b] = z[:, n:n + n * p].reshape(n_t, p, n)
+        if tend[b] != t0[b] or sens0.any():     # the gradient's system: S = 0, S0 = I at tend
+            zr = run(tend[b], tv, np.concatenate([zs[tend[b]][:n], np.zeros(n * p), np.eye(n).ravel()]), ps[b], prb)
+            z = np.array([zr[t] for t in tv.tolist()])
+        S = z[:, n:n + n * p].reshape(n_t, p, n)
+        S0 = z[:, n + n * p:].reshape(n_t, n, n)        # [k, j(y(tend) index), i(state)]
+        out["grad_params"][b] = np.einsum("ki,kpi->p", g, S)
+        out["grad_y_tend"][b] = np.einsum("ki,kji->j", g, S0)
+        out["d_tvals"][b] = [f(t, out["y_out"][b, k], ps[b], prb) @ g[k] for k, t in enumerate(tv)]
+        # d_tvals against a central difference of the truth solution: y(t_k +- h) of the plain ODE from (t0, y0)
+        h = 1e-4
+        ta, y0b = t0[b], y0[b]
+        fwd_t = np.unique(np.concatenate([tv + h, tv - h]))
+        lo, hi = fwd_t[fwd_t < ta], fwd_t[fwd_t >= ta]
+        ys = {}
+        for part, end in ((hi, hi[-1]), (lo[::-1], lo[0] if len(lo) else None)):
+            if not len(part):
+                continue
+            sol = solve_ivp(lambda t, yv: f(t, yv, ps[b], prb), (ta, end), y0b, method="DOP853", t_eval=part,
+                            rtol=rtol, atol=atol)
+            assert sol.success, sol.message
+            ys.update(zip(part.tolist(), sol.y.T))
+        fd = np.array([(ys[(t + h)] - ys[(t - h)]) @ g[k] / ((t + h) - (t - h)) for k, t in enumerate(tv)])
+        err = np.max(np.abs(fd - out["d_tvals"][b])) / np.abs(out["d_tvals"][b]).max()
+        assert err < 1e-6, (b, err)
+        print("  times instance %d: t0 %.6g, tend - t0 %.3g, span %.3g, d_tvals vs central difference %.1e"
+              % (b, t0[b], tend[b] - t0[b], tv[-1] - t0[b], err), flush=True)
+    return out
+
+
+def _times_rows(B, n_t, t0, span, rng):
+    """Grids t0 + span * sorted uniforms, with the edge rows of ``times_truth`` (its docstring names them)."""
+    tv = t0[:, None] + span[:, None] * np.sort(rng.uniform(0.02, 1.0, (B, n_t)), axis=1)
+    tend = t0.copy()
+    for b in range(B):
+        if b % 4 == 0:
+            tv[b, 0] = t0[b]                            # first output time at t0
+        elif b % 4 == 1:
+            tv[b, :2] = t0[b]                           # t0 repeated at the head of the row
+        elif b % 4 == 2:
+            tend[b] = t0[b] + 0.5 * (tv[b, 0] - t0[b])  # backward pass stops before the forward start
+        if b % 3 == 0:
+            tv[b, n_t // 2 + 1] = tv[b, n_t // 2]       # a repeated output time inside the row
+    return tv, tend
+
+
+def times_truth():
+    """truth_times_<name>.npz: per-instance start times, output grids and backward end times on the two models whose
+    right-hand side reads t -- ``forcing`` (B-spline input on [0, 10], expit(k (t - t_mid))) and ``misc`` (sin t).
+
+    Inputs t0 [B], tvals [B, n_t], tend [B], grads [B, n_t, n], y0, ps, pr (the models' own draws); truth y_out, sens,
+    grad_params, grad_y_tend, d_tvals (``truth_times_batch``).  Keys ``one_*``: the same for a few rows with n_t = 1.
+
+    Rows (B = 28, n_t = 8):
+      * every b % 4 == 0: tvals[b, 0] == t0[b];  b % 4 == 1: tvals[b, 0] == tvals[b, 1] == t0[b];
+        b % 4 == 2: t0[b] < tend[b] < tvals[b, 0] (tend halfway);  otherwise tend[b] == t0[b];
+      * every b % 3 == 0: tvals[b, 5] == tvals[b, 4] (a repeated output time inside the row);
+      * forcing: t0 spread over [-3, 7] (windows straddle the spline's support edge 0 and its knots); spans 0.02 on
+        rows 0-3, 20 on rows 4-7, log-uniform in between on the rest (a factor 10^3 inside one wavefront); the
+        cotangents of the rows shorter than 1 are scaled by 1 / span;
+      * misc: t0 ~ 1e3 on rows 0-7 and ~ 1e5 on rows 8-15 with spans ~ 10 (UROUND |t| is no longer negligible in the
+        initial step and the too-close test), t0 in [-5, 5] on the rest; spans 0.01 on rows 16-19.
+    n_t = 1 rows (``one_*``, B = 6): tvals[b, 0] == t0[b] on row 0 (no forward step: its backward pass is CV_NO_FWD,
+    the truth gradient there is not a solver's), tend halfway on rows 1 and 4."""
+    for name, batch, B, n_t in (("forcing", forcing_batch, 28, 8), ("misc", misc_batch, 28, 8)):
+        prob = make(name)
+        n = prob.n_states
+        rng = np.random.default_rng(7 if name == "forcing" else 11)
+        d = batch(B)
+        if name == "forcing":
+            t0 = rng.uniform(-3.0, 7.0, B)
+            span = 10.0 ** rng.uniform(np.log10(0.02), np.log10(20.0), B)
+            span[:4], span[4:8] = 0.02, 20.0
+        else:
+            t0 = np.concatenate([1e3 + rng.uniform(-5.0, 5.0, 8), 1e5 + rng.uniform(-5.0, 5.0, 8),
+                                 rng.uniform(-5.0, 5.0, B - 16)])
+            span = rng.uniform(8.0, 12.0, B)
+            span[16:20] = 0.01
+        tvals, tend = _times_rows(B, n_t, t0, span, rng)
+        # cotangents scaled by 1 / span on the short rows: their dL/dp stays O(1), as on the long rows, instead of
+        # O(span) -- the absolute quadrature tolerance (1e-8) would otherwise be the error's floor there
+        grads = _cotangents(B, n_t, n) * np.maximum(1.0, 1.0 / (tvals[:, -1] - t0))[:, None, None]
+        res = truth_times_batch(prob, d["y0"], d["ps"], d["pr"], t0, tvals, tend, grads)
+        # n_t = 1
+        B1 = 6
+        t01 = t0[:B1] + 0.25
+        tv1 = t01[:, None] + rng.uniform(0.5, 3.0, (B1, 1))
+        tv1[0, 0] = t01[0]
+        tend1 = t01.copy()
+        tend1[[1, 4]] = 0.5 * (t01[[1, 4]] + tv1[[1, 4], 0])
+        g1 = _cotangents(B1, 1, n)
+        res1 = truth_times_batch(prob, d["y0"][:B1], d["ps"][:B1], d["pr"], t01, tv1, tend1, g1)
+        np.savez(os.path.join(GOLD, "truth_times_%s.npz" % name), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=t0,
+                 tvals=tvals, tend=tend, grads=grads, **res,
+                 one_t0=t01, one_tvals=tv1, one_tend=tend1, one_grads=g1, **{"one_" + k: v for k, v in res1.items()})
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
+    if "--times" in sys.argv:
+        times_truth()
+        return
     if "--transcendental" in sys.argv:          # only the round-6 fixtures (the others are unchanged)
         transcendental_truth()
         return
