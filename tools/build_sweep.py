@@ -29,6 +29,10 @@ def _compile(name, kind):
         out = _native.build_code_object(src, sens=True)
     elif kind == "conservative":        # the differential guard's partner build (tests/test_guard.py runs the sweep's shapes through it)
         out = _native.build_code_object(src, compact=_native.default_compact_trajectory(src), safe=True)
+    elif kind == "plain":               # ``Solver(prob)``: forward only, full trajectory records (the pinned shapes' device test)
+        out = _native.build_code_object(src)
+    elif kind == "plain conservative":
+        out = _native.build_code_object(src, safe=True)
     elif kind.startswith("small-batch"):     # AdjointSolver's mappings for small batches (_native.small_batch_group)
         out = _native.build_code_object(src, compact=True, group=kind.split(":")[1])
     else:
@@ -38,7 +42,7 @@ def _compile(name, kind):
 
 def build(names=None, verbose=True):
     from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
-    from tools.sweep_cases import ADJOINT_CASES, SENS_CASES
+    from tools.sweep_cases import ADJOINT_CASES, PINNED_CASES, SENS_CASES
     adj = [c[0] for c in ADJOINT_CASES if names is None or c[0] in names]
     sens = [c[0] for c in SENS_CASES if names is None or c[0] in names]
     every = sorted(set(adj) | set(sens), key=lambda s: (len(s), s))
@@ -48,7 +52,8 @@ def build(names=None, verbose=True):
             if verbose and dt > 5:
                 print("problem [%s]: %.0f s of sympy" % (name, dt))
     jobs = [(n, "oracle") for n in every] + [(n, "adjoint") for n in adj] + [(n, "sens") for n in sens] \
-        + [(n, "conservative") for n in adj] + [(n, "small-batch:" + g) for n in adj if n == "rn5_8" for g in ("wave16", "wave8", "wave4")]
+        + [(n, "conservative") for n in adj] + [(n, k) for n in adj if n in PINNED_CASES for k in ("plain", "plain conservative")] \
+        + [(n, "small-batch:" + g) for n in adj if n == "rn5_8" for g in ("wave16", "wave8", "wave4")]
     failed = []
     with ThreadPoolExecutor(max_workers=workers) as pool:           # compiler subprocesses: threads
         futs = [(j, pool.submit(_compile, *j)) for j in jobs]

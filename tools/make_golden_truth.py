@@ -124,17 +124,12 @@ def transcendental_truth():
 
 
 def sweep_truth():
-    """truth_sweep_<name>.npz for two shapes of the parity sweep (tests/test_shape_sweep.py): ``lv12`` (2 states, 12
-    differentiated parameters) and ``rn12_4`` (12 states): 4 draws each of the sweep's own batch."""
-    from tools.problem_cache import spec_of
-    from tools.sweep_cases import batch_of
-    for name in ("lv12", "rn12_4"):
-        s = spec_of(name)
-        prob = SympyProblem(s["params"], s["states"], s["rhs"], s["derivative_params"])
-        d = batch_of(name, 4)
-        y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
-        np.savez(os.path.join(GOLD, "truth_sweep_%s.npz" % name), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
-                 tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
+    """truth_sweep_<name>.npz for every shape of the parity sweep (tests/test_shape_sweep.py, tests/test_sweep_truth.py):
+    4 draws each of the sweep's own batch -- from the hand-written closed form of the sweep's model families, not from
+    this module's lambdified ``prob._sym_*`` (tools/make_golden_truth_sweep.py; ``truth_batch`` here stays the second,
+    symbolic derivation the tests compare it with on ``lv12`` and ``rn12_4``)."""
+    from tools import make_golden_truth_sweep
+    make_golden_truth_sweep.main()
 
 
 def plain_rhs(prob):

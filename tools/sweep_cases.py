@@ -42,6 +42,12 @@ SENS_CASES = [
     ("rn21_17", 12), ("rn22_1", 24),
 ]
 
+#: shapes whose callbacks are also pinned to values of the reference's own symbolic pipeline
+#: (tests/golden/callbacks_sweep.json, tools/make_golden_callbacks_sweep.py): one per kernel family, plus the register
+#: kernel's largest shape, an 8-lane lean shape and the zero-run loops' only user.  Their device test runs the plain
+#: forward build (``Solver(prob)``), which ``tools/build_sweep.py`` therefore pre-compiles as well.
+PINNED_CASES = ["lv12", "rn7_4", "rnb15_9", "rn22_33", "rn65_4", "rn5_8", "rn17_4", "chain256"]
+
 
 def batch_of(name, B):
     """Inputs of case ``name`` (tools/problems.py generators)."""
