@@ -13,11 +13,19 @@ N > 1  : `python bench.py --gpus N` starts N ranks itself (a child torch.distrib
 
 Prints ONE JSON line (rank 0) with the contract fields plus
   roofline     : dominant kernel (sa_k_backward): SURVEY 8(d) algorithmic HBM bytes / HIP-event duration vs
-                 8 TB/s, and a `valu` block (the roofline that actually binds: fp64 vector rate)
+                 8 TB/s, and a `valu` block (the roofline that actually binds: fp64 vector rate) -- from the
+                 timed steps' own HIP events and the committed counter profile, no run of its own
+
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) does what that line needs and nothing else: set up,
+warm up, time the N steps, write --dump-outputs, print.  Everything that measures or checks something else is
+behind `--full` (N = 1; `--no-cpu-baseline` / `--no-extra-configs` switch parts of it off again):
+  truth_gradient_error : the timed batch's first gradients against the committed truth fixture
   cpu_baseline : the CPU oracle (oracle/cvodes_oracle.c, "port") timed on the host cores, bounded sample,
                  all-core and 1-core figures, and the libsundials_cvodes probe
-  configs      : (N = 1) the other BASELINE configurations -- Robertson, SEIR, 100-state network -- a few
+  host_api     : the same step through the product's Python API, numpy arrays in and out
+  configs      : the other BASELINE configurations -- Robertson, SEIR, 100-state network -- a few
                  steps each with kernel times, failed-instance counts and their own bounded CPU baselines
+  first_use    : what a new model costs before its first batch (derivation + code objects from a cold cache)
 """
 from __future__ import annotations
 
@@ -586,7 +594,7 @@ def summarise(name, prob, w, B, world, args, elapsed, fwd_ms, bwd_ms, res, faile
     if res.get("guard") is not None:
         # what the differential guard found for this code object (verdict file next to it, or this run's check)
         out["guard"] = res["guard"]
-    err = truth_gradient_error(name, res)
+    err = truth_gradient_error(name, res) if getattr(args, "full", False) else None      # (a check: --full only)
     if err:
         out["truth_gradient_error"] = err
     return out
@@ -765,6 +773,26 @@ def extra_configs(args):
     return rows
 
 
+def full_report(args, out):
+    """--full (N = 1): everything the line carries beyond the headline figure, each part a measurement of its own
+    made after the timed steps."""
+    name, w = args.workload, WORKLOADS[args.workload]
+    if not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(name, make_problem(name), w)
+    if args.no_extra_configs:
+        return
+    try:
+        out["host_api"] = host_api(name, make_problem(name), w, args.batch or w["batch"])
+    except Exception as exc:        # noqa: BLE001 -- the headline line must not depend on it
+        out["host_api"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
+    if name == "lv":
+        out["configs"] = extra_configs(args)
+    try:
+        out["first_use"] = first_use(name)
+    except Exception as exc:        # noqa: BLE001 -- the headline line must not depend on it
+        out["first_use"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -772,8 +800,13 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=0, help="instances per GPU (default: the workload's BASELINE batch)")
     ap.add_argument("--workload", default="lv", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="--gpus 1: after the timed steps also measure and check everything else -- the CPU baselines, "
+                         "the same step through the host API, the other BASELINE configurations, the cold-cache cost of "
+                         "a new model, the gradients against the truth fixture (minutes; off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baselines")
+    ap.add_argument("--no-extra-configs", action="store_true",
+                    help="--full: without the host API, the other configurations and the cold-cache cost")
     ap.add_argument("--single-process", action="store_true",
                     help="drive the --gpus N devices from THIS process (one engine + host thread per device) instead "
                          "of one process per GPU")
@@ -816,22 +849,10 @@ def main(argv=None):
             launch_ranks(args, argv)                  # does not return
         out = run_rank(args)
     if out is not None:
+        out["full"] = bool(args.full)
         if args.gpus == 1:
-            if not args.no_cpu_baseline:
-                out["cpu_baseline"] = cpu_baseline(args.workload, make_problem(args.workload), WORKLOADS[args.workload])
-            if not args.no_extra_configs:
-                try:
-                    out["host_api"] = host_api(args.workload, make_problem(args.workload), WORKLOADS[args.workload],
-                                               args.batch or WORKLOADS[args.workload]["batch"])
-                except Exception as exc:        # noqa: BLE001 -- the headline line must not depend on it
-                    out["host_api"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-            if not args.no_extra_configs and args.workload == "lv":
-                out["configs"] = extra_configs(args)
-            if not args.no_extra_configs:
-                try:
-                    out["first_use"] = first_use(args.workload)
-                except Exception as exc:        # noqa: BLE001 -- the headline line must not depend on it
-                    out["first_use"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
+            if args.full:
+                full_report(args, out)
         else:
             # the contract times the CPU baseline at N = 1 only; keep the pointer so an N > 1 line is self-describing
             out["cpu_baseline"] = {"value": None, "unit": "solves/s", "cores": usable_cores(), "kind": "port",

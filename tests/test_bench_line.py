@@ -1,6 +1,8 @@
 """bench.py's bookkeeping that needs no GPU: the committed counter profile is only used when it describes the build,
 batch and record format of the run at hand, the truth-gradient error of the timed batch's first draws,
-the number of timed steps and what --dump-outputs writes."""
+the number of timed steps, what --dump-outputs writes, and that a plain run measures the headline figure alone
+(everything else behind --full)."""
+import json
 import os
 
 import numpy as np
@@ -79,6 +81,54 @@ def test_steps_are_the_timed_steps_and_the_dump_is_the_last_step(tmp_path):
     for bad in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", str(tmp_path)]):
         with pytest.raises(SystemExit):
             bench.parse_args(bad)
+
+
+def _main_line(bench, monkeypatch, capsys, argv):
+    """The line `bench.main(argv)` prints with a counting engine, and the --full parts it ran (in order)."""
+    ran = []
+    monkeypatch.setattr(bench, "GpuEngine", _CountingEngine)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: ran.append("cpu_baseline") or {"value": 1.0})
+    monkeypatch.setattr(bench, "host_api", lambda *a, **k: ran.append("host_api") or {"solves_per_s": 1.0})
+    monkeypatch.setattr(bench, "extra_configs", lambda *a, **k: ran.append("configs") or {})
+    monkeypatch.setattr(bench, "first_use", lambda *a, **k: ran.append("first_use") or {})
+    monkeypatch.setattr(bench, "truth_gradient_error", lambda *a, **k: ran.append("truth") or {"draws": 16})
+    _CountingEngine.made.clear()
+    bench.main(argv)
+    (text,) = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    return json.loads(text), ran
+
+
+FULL_ONLY = ("cpu_baseline", "host_api", "configs", "first_use", "truth_gradient_error")
+
+
+def test_a_plain_run_measures_the_headline_figure_alone(monkeypatch, capsys):
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "40"]
+    for extra in ([], ["--no-cpu-baseline"], ["--no-extra-configs"]):
+        line, ran = _main_line(bench, monkeypatch, capsys, argv + extra)
+        assert ran == [] and not any(k in line for k in FULL_ONLY) and line["full"] is False
+        (eng,) = _CountingEngine.made
+        assert eng.steps == 5                       # warm-up + timed steps, nothing else stepped an engine
+        assert line["unit"] == "solves/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert line["metric"].startswith("fp64 forward+adjoint ODE solves/sec") and line["steps"] == 3
+        assert abs(line["value"] - 40 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        assert {"roofline", "work", "config", "build"} <= set(line)      # (figures of the timed steps themselves stay)
+
+
+def test_full_runs_every_other_measurement_after_the_timed_steps(monkeypatch, capsys):
+    import bench
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "40", "--full"]
+    line, ran = _main_line(bench, monkeypatch, capsys, argv)
+    assert ran == ["truth", "cpu_baseline", "host_api", "configs", "first_use"]
+    assert all(k in line for k in FULL_ONLY) and line["full"] is True
+    assert _CountingEngine.made[0].steps == 5 and line["steps"] == 3 and line["warmup"] == 2
+    line, ran = _main_line(bench, monkeypatch, capsys, argv + ["--no-cpu-baseline"])
+    assert ran == ["truth", "host_api", "configs", "first_use"] and "cpu_baseline" not in line
+    line, ran = _main_line(bench, monkeypatch, capsys, argv + ["--no-extra-configs"])
+    assert ran == ["truth", "cpu_baseline"]
+    line, ran = _main_line(bench, monkeypatch, capsys, argv + ["--workload", "seir"])     # (configs: the headline workload's)
+    assert ran == ["truth", "cpu_baseline", "host_api", "first_use"]
 
 
 def test_dump_outputs_keeps_a_fixed_sample_of_rows_within_the_size_bound(tmp_path, monkeypatch):

@@ -239,3 +239,29 @@ def test_bench_rank_under_an_rccl_process_group_of_one(tmp_path):
     assert g["n_gpus"] == 1 and g["config"]["failed_instances"] == 0 and g["value"] > 0
     for key in ("fwd_steps_mean", "bwd_steps_mean", "stored_points_mean"):
         assert g["work"][key] == p["work"][key]
+
+
+def test_a_plain_bench_run_spends_at_most_30_s_outside_its_steps():
+    """`bench.py --gpus 1 --steps N --warmup W` without --full does what the headline figure needs and nothing else:
+    the whole run, from process start to exit, less (N + W) x ms_per_step -- imports, problem and batch set-up, code
+    object, arena, the guard's first step, the result line -- stays within 30 s, and the line carries none of the
+    --full blocks."""
+    import json
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 3, 1
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)]
+    t0 = time.perf_counter()
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert res.returncode == 0, res.stderr[-3000:]
+    line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    outside = wall - (steps + warmup) * line["ms_per_step"] * 1e-3
+    print("plain bench run: %.2f s in all, %.2f ms per step, %.2f s outside the steps" % (wall, line["ms_per_step"], outside))
+    assert line["full"] is False and line["steps"] == steps and line["warmup"] == warmup and line["value"] > 0
+    assert line["config"]["failed_instances"] == 0
+    for key in ("cpu_baseline", "host_api", "configs", "first_use", "truth_gradient_error"):
+        assert key not in line
+    assert outside <= 30.0, outside
