@@ -242,9 +242,17 @@ int sa_eval_callbacks(sa_solver *s, int mem, int32_t npts, const double *t, cons
                       const double *lam, const double *ps, const double *pr, double *rhs, double *jac,
                       double *adj, double *quad, double *adjjac, int32_t *codes);
 
+/* ---- test hooks ---- */
 /* Device arithmetic probe used by the parity tests (deterministic pow, sqrt, divide). Host arrays. */
 int sa_math_probe(sa_solver *s, int32_t n, const double *x, const double *y, double *pow_out,
                   double *sqrt_out, double *div_out);
+/* The arena plan of a batch that is not resident, on the caller's numbers (host arithmetic only, no device needed):
+   counts [B] points per instance, record_bytes per point, budget in bytes.  Out: counts_out [B] (the counts, zero
+   where an instance was taken out because its 64-instance group exceeds the budget even alone), full_idx [B] /
+   *n_full (those instances), cuts [(B+63)/64] / *n_cuts (the end of every tile; every cut but the last a multiple
+   of 64) and *balanced (1: the equal-sized alternative replaced the greedy cuts; may be NULL). */
+int sa_plan_tiles(int32_t B, const int32_t *counts, int64_t record_bytes, int64_t budget, int32_t *counts_out,
+                  int32_t *full_idx, int32_t *n_full, int64_t *cuts, int32_t *n_cuts, int32_t *balanced);
 
 /* Trajectory arena of the last sa_solve_forward_batch / sa_solve_backward_batch pair: bytes of the largest arena
    allocation used, number of re-integrated tiles so far on this handle, and whether the last forward batch is

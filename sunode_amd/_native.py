@@ -533,6 +533,8 @@ def load_library() -> ctypes.CDLL:
                                                 i32, _dp, i64, _dp, _dp, _dp, _dp, _dp, _dp]
     L.sa_eval_callbacks.argtypes = [vp, ctypes.c_int, i32] + [_dp] * 11
     L.sa_math_probe.argtypes = [vp, i32] + [_dp] * 5
+    L.sa_plan_tiles.argtypes = [i32, _dp, i64, i64, _dp, _dp, ctypes.POINTER(i32), _dp, ctypes.POINTER(i32),
+                                ctypes.POINTER(i32)]
     L.sa_arena_info.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32)]
     L.sa_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.sa_device_count.argtypes = [ctypes.POINTER(i32)]
@@ -547,7 +549,7 @@ def load_library() -> ctypes.CDLL:
                  "sa_solve_forward_batch", "sa_solve_backward_batch", "sa_solve_backward_batch_all",
                  "sa_solve_batch_times", "sa_solve_forward_batch_times", "sa_solve_sens_batch_times",
                  "sa_solve_backward_batch_times", "sa_eval_callbacks", "sa_math_probe", "sa_last_kernel_ms", "sa_set_stream", "sa_synchronize",
-                 "sa_arena_info", "sa_device_count", "sa_device_memory"):
+                 "sa_plan_tiles", "sa_arena_info", "sa_device_count", "sa_device_memory"):
         getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -558,7 +560,7 @@ EXPORTED_SYMBOLS = ["sa_abi_version", "sa_last_error", "sa_solver_create", "sa_s
                     "sa_solve_forward_batch",
                     "sa_solve_backward_batch", "sa_solve_backward_batch_all",
                     "sa_solve_batch_times", "sa_solve_forward_batch_times", "sa_solve_sens_batch_times",
-                    "sa_solve_backward_batch_times", "sa_eval_callbacks", "sa_math_probe",
+                    "sa_solve_backward_batch_times", "sa_eval_callbacks", "sa_math_probe", "sa_plan_tiles",
                     "sa_last_kernel_ms", "sa_arena_info",
                     "sa_set_stream", "sa_synchronize", "sa_device_count", "sa_device_memory",
                     "sa_solver_attach_guard", "sa_guard_state"]
@@ -824,6 +826,7 @@ class NativeSolver:
 
     def solve_sens(self, mem, ism, scaling, B, y0, ps, pr, rem_stride, sens0, t0, tvals, n_t, y_out, sens_out,
                    status, stats, t0_stride=None, tvals_stride=None):
+        done = self._torch_guard(y0, ps, pr, sens0, tvals, y_out, sens_out, status, stats, t0)
         if t0_stride is None and tvals_stride is None:
             rc = self.L.sa_solve_sens_batch(self._h, mem, int(ism), _addr(scaling), B, _addr(y0), _addr(ps),
                                             _addr(pr), rem_stride, _addr(sens0), float(t0), _addr(tvals), n_t,
@@ -835,6 +838,8 @@ class NativeSolver:
                                                   _addr(tvals), int(tvals_stride or 0), n_t,
                                                   _addr(y_out), _addr(sens_out), _addr(status), _addr(stats))
         self._check(rc)
+        if done:
+            done()
         if self._guard_open:
             self._guard_poll()
 

@@ -132,6 +132,7 @@ struct sa_solver {
     DevBuf d_overflow;             /* int32: max point count of the instances that outgrew traj_rows (0: none) */
     size_t budget = 0;             /* arena budget of the last forward call (the backward call must use the same) */
     std::vector<int32_t> full_idx; /* instances whose 64-instance group exceeds the budget: backward status ARENA_FULL */
+    std::vector<int64_t> cuts;     /* tiled mode: end of every tile (plan_tiles, settled with full_idx in resolve_forward) */
     int64_t stat_tiles = 0, stat_arena_bytes = 0;
     /* staging for SA_MEM_HOST calls */
     DevBuf s_y0, s_ps, s_pr, s_tvals, s_yout, s_status, s_stats, s_grads, s_gout, s_lout, s_t0, s_tend;
@@ -445,6 +446,103 @@ static size_t arena_budget(const sa_solver *s)
 
 static size_t record_bytes(const sa_solver *s) { return sizeof(double) * (size_t)s->rec_doubles; }
 
+/* do n_inst instances (rounded up to whole 64-instance groups) of `rows` records each fit the budget? */
+static bool fits_budget(int64_t n_inst, int64_t rows, size_t rec, size_t budget)
+{
+    return (size_t)round64(n_inst) * (size_t)rows * rec <= budget;
+}
+
+/* rows a tile [lo, hi) of the batch needs (lo on a group boundary): its largest point count, never less than the two
+   rows every store-mode launch has -- and whether round64(hi - lo) instances of that many records fit the budget */
+static bool tile_fits(const std::vector<int32_t> &gmax, int64_t lo, int64_t hi, size_t rec, size_t budget, int64_t *rows_out)
+{
+    int64_t r2 = 2;
+    for (int64_t g = lo / 64; g < (hi + 63) / 64; g++) if (gmax[(size_t)g] > r2) r2 = gmax[(size_t)g];
+    if (rows_out) *rows_out = r2;
+    return fits_budget(hi - lo, r2, rec, budget);
+}
+
+/* largest point count of every 64-instance group (at least 2) */
+static std::vector<int32_t> group_max(int64_t B, const int32_t *np)
+{
+    std::vector<int32_t> gmax((size_t)((B + 63) / 64), 2);
+    for (int64_t i = 0; i < B; i++)
+        if (np[i] > gmax[(size_t)(i / 64)]) gmax[(size_t)(i / 64)] = np[i];
+    return gmax;
+}
+
+/* The arena decisions of a batch that is not resident, as integer arithmetic alone (no HIP calls; the tests reach it
+   through sa_plan_tiles).  np [B]: points per instance, from the forward call.
+     taken out  an instance whose 64-instance group cannot fit the budget even alone: listed in full_idx, its count
+                zeroed (it takes no part in any tile's rows)
+     cuts       the end of every tile: as few tiles as the budget allows (greedy over 64-instance groups), then
+                balanced -- equal-sized tiles keep every launch wide enough to fill the chip -- as long as each
+                still fits (*balanced says which)
+   Returns the largest count seen (the handle's rows hint). */
+static int32_t plan_tiles(int64_t B, int32_t *np, size_t rec, size_t budget, std::vector<int32_t> &full_idx,
+                          std::vector<int64_t> &cuts, bool *balanced)
+{
+    full_idx.clear();
+    cuts.clear();
+    if (balanced) *balanced = false;
+    const int64_t group_rows = (int64_t)(budget / ((size_t)64 * rec));
+    int32_t seen = 0;
+    for (int64_t i = 0; i < B; i++) {
+        if (np[i] > seen) seen = np[i];
+        if (np[i] > group_rows) {                   /* (more than traj_capacity points: already failed in the kernel) */
+            np[i] = 0;
+            full_idx.push_back((int32_t)i);
+        }
+    }
+    const std::vector<int32_t> gmax = group_max(B, np);
+    for (int64_t lo_ = 0; lo_ < B;) {               /* greedy, one pass with a running maximum */
+        int64_t hi_ = (lo_ + 64 < B) ? lo_ + 64 : B;
+        int64_t r2 = gmax[(size_t)(lo_ / 64)];
+        while (hi_ < B) {
+            const int64_t nhi = (hi_ + 64 < B) ? hi_ + 64 : B;
+            const int64_t rn = gmax[(size_t)(hi_ / 64)] > r2 ? gmax[(size_t)(hi_ / 64)] : r2;
+            if (!fits_budget(nhi - lo_, rn, rec, budget)) break;
+            hi_ = nhi; r2 = rn;
+        }
+        cuts.push_back(hi_);
+        lo_ = hi_;
+    }
+    if (cuts.size() > 1) {                          /* balanced alternative with the same number of tiles */
+        const int64_t per = round64((B + (int64_t)cuts.size() - 1) / (int64_t)cuts.size());
+        std::vector<int64_t> even;
+        bool ok = true;
+        for (int64_t lo_ = 0; lo_ < B && ok; lo_ += per) {
+            const int64_t hi_ = (lo_ + per < B) ? lo_ + per : B;
+            ok = tile_fits(gmax, lo_, hi_, rec, budget, nullptr);
+            even.push_back(hi_);
+        }
+        if (ok && even.size() <= cuts.size()) {
+            cuts.swap(even);
+            if (balanced) *balanced = true;
+        }
+    }
+    return seen;
+}
+
+/* test hook (include/sunode_amd.h): plan_tiles on the caller's counts.  counts_out [B], full_idx [B], cuts [(B+63)/64]. */
+extern "C" int sa_plan_tiles(int32_t B, const int32_t *counts, int64_t rec_bytes, int64_t budget, int32_t *counts_out,
+                             int32_t *full_idx, int32_t *n_full, int64_t *cuts, int32_t *n_cuts, int32_t *balanced)
+{
+    if (B < 0 || rec_bytes <= 0 || budget < 0) return fail(SA_ERR_ARG, "sa_plan_tiles: B >= 0, record_bytes > 0, budget >= 0");
+    if (!counts || !counts_out || !full_idx || !n_full || !cuts || !n_cuts) return fail(SA_ERR_ARG, "null argument");
+    std::vector<int32_t> np(counts, counts + B), full;
+    std::vector<int64_t> c;
+    bool bal = false;
+    (void)plan_tiles(B, np.data(), (size_t)rec_bytes, (size_t)budget, full, c, &bal);
+    for (int32_t i = 0; i < B; i++) counts_out[i] = np[(size_t)i];
+    for (size_t i = 0; i < full.size(); i++) full_idx[i] = full[i];
+    for (size_t i = 0; i < c.size(); i++) cuts[i] = c[i];
+    *n_full = (int32_t)full.size();
+    *n_cuts = (int32_t)c.size();
+    if (balanced) *balanced = bal ? 1 : 0;
+    return SA_OK;
+}
+
 struct FwdLaunch {
     int mode; int32_t B, n_t, rem_stride, rows; int64_t stride; double t0;
     const double *y0, *ps, *pr, *tvals; double *y_out; int32_t *status; int64_t *stats; int32_t *traj_np;
@@ -739,18 +837,11 @@ static int resolve_forward(sa_solver *s)
     HIP_TRY(hipMemcpyAsync(s->h_np.data(), s->traj_np.p, sizeof(int32_t) * nB, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipMemcpyAsync(s->h_scratch.data(), s->fwd_status.p, sizeof(int32_t) * nB, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    const int64_t group_rows = (int64_t)(s->budget / ((size_t)64 * rec));
-    int32_t seen = 0;
-    for (size_t i = 0; i < nB; i++) {
-        if (s->h_np[i] > seen) seen = s->h_np[i];
-        if (s->h_np[i] > group_rows) {              /* (more than traj_capacity points: already failed in the kernel) */
-            s->h_np[i] = 0;
-            s->h_scratch[i] = SA_STATUS_ARENA_FULL;
-            s->full_idx.push_back((int32_t)i);
-        }
-    }
-    if (!s->full_idx.empty())                       /* the library-owned copy: the backward kernel answers CV_NO_FWD */
+    const int32_t seen = plan_tiles((int64_t)nB, s->h_np.data(), rec, s->budget, s->full_idx, s->cuts, nullptr);
+    if (!s->full_idx.empty()) {                     /* the library-owned copy: the backward kernel answers CV_NO_FWD */
+        for (int32_t i : s->full_idx) s->h_scratch[(size_t)i] = SA_STATUS_ARENA_FULL;
         HIP_TRY(hipMemcpyAsync(s->fwd_status.p, s->h_scratch.data(), sizeof(int32_t) * nB, hipMemcpyHostToDevice, s->stream));
+    }
     if (seen > s->rows_hint) s->rows_hint = seen;
     return SA_OK;
 }
@@ -839,51 +930,15 @@ static int backward_common(sa_solver *s, int mem, int32_t B, const double *ps, c
         /* tiled: re-integrate the forward problem tile by tile with exactly sized storage, adjoint per tile */
         const size_t rec = record_bytes(s), budget = s->budget;      /* the forward call's (not re-evaluated) */
         const size_t np_ = (size_t)s->p, nn = (size_t)s->n;
-        /* tile boundaries: as few tiles as the budget allows (greedy over 64-instance groups), then balanced --
-           equal-sized tiles keep every launch wide enough to fill the chip -- as long as each still fits */
-        const int64_t n_groups = (B + 63) / 64;
-        std::vector<int32_t> gmax((size_t)n_groups, 2);            /* largest point count of every 64-instance group */
-        for (int64_t i = 0; i < B; i++)
-            if (s->h_np[(size_t)i] > gmax[(size_t)(i / 64)]) gmax[(size_t)(i / 64)] = s->h_np[(size_t)i];
-        auto rows_of = [&](int64_t lo_, int64_t hi_) {             /* lo_, hi_ on group boundaries (hi_ may be B) */
-            int64_t r2 = 2;
-            for (int64_t g = lo_ / 64; g < (hi_ + 63) / 64; g++) if (gmax[(size_t)g] > r2) r2 = gmax[(size_t)g];
-            return r2;
-        };
-        auto fits = [&](int64_t lo_, int64_t hi_, int64_t *rows_out) {
-            const int64_t r2 = rows_of(lo_, hi_);
-            if (rows_out) *rows_out = r2;
-            return (size_t)round64(hi_ - lo_) * (size_t)r2 * rec <= budget;
-        };
-        std::vector<int64_t> cuts;                  /* greedy, one pass with a running maximum */
-        for (int64_t lo_ = 0; lo_ < B;) {
-            int64_t hi_ = (lo_ + 64 < B) ? lo_ + 64 : B;
-            int64_t r2 = gmax[(size_t)(lo_ / 64)];
-            while (hi_ < B) {
-                const int64_t nhi = (hi_ + 64 < B) ? hi_ + 64 : B;
-                const int64_t rn = gmax[(size_t)(hi_ / 64)] > r2 ? gmax[(size_t)(hi_ / 64)] : r2;
-                if ((size_t)round64(nhi - lo_) * (size_t)rn * rec > budget) break;
-                hi_ = nhi; r2 = rn;
-            }
-            cuts.push_back(hi_);
-            lo_ = hi_;
-        }
-        if (cuts.size() > 1) {                      /* balanced alternative with the same number of tiles */
-            const int64_t per = round64((B + (int64_t)cuts.size() - 1) / (int64_t)cuts.size());
-            std::vector<int64_t> even;
-            bool ok = true;
-            for (int64_t lo_ = 0; lo_ < B && ok; lo_ += per) {
-                const int64_t hi_ = (lo_ + per < B) ? lo_ + per : B;
-                ok = fits(lo_, hi_, nullptr);
-                even.push_back(hi_);
-            }
-            if (ok && even.size() <= cuts.size()) cuts.swap(even);
-        }
+        /* tile boundaries: plan_tiles, settled by resolve_forward together with the instances taken out */
+        const std::vector<int64_t> &cuts = s->cuts;
+        const std::vector<int32_t> gmax = group_max(B, s->h_np.data());
+        if (cuts.empty() || cuts.back() != B) return fail(SA_ERR_INTERNAL, "tiled backward call without a tile plan for this batch");
         int64_t lo = 0;
         for (size_t ti = 0; ti < cuts.size(); ti++) {
             const int64_t hi = cuts[ti];
             int64_t rows = 2;
-            (void)fits(lo, hi, &rows);
+            (void)tile_fits(gmax, lo, hi, rec, budget, &rows);
             const int32_t tB = (int32_t)(hi - lo);
             const int64_t stride = round64(tB);
             {   /* a batch that turns out to fit as ONE tile will be resident from the next call on: allocate the rows
