@@ -22,8 +22,13 @@ into the generated header when used) instead of libm / ocml, so that host and
 device evaluate bit-identical arithmetic (both sides are compiled with
 ``-ffp-contract=off``); this is what makes the step/order bookkeeping of the
 HIP integrator comparable bit-for-bit with the CPU oracle -- for rational AND
-transcendental right-hand sides.  Functions outside that list (``LIBM_ONLY``)
-still compile, through libm / ocml, without the bit-equality guarantee.
+transcendental right-hand sides.  ``asin / acos / atan / atan2 / asinh / acosh /
+atanh / erf / erfc`` are printed the same way, as calls of ``csrc/sa_math_inv.h``:
+a second block, embedded after the first only when a callback calls one of its
+functions, so that the headers of models without them keep their text (and with
+it their cache keys and code objects).  Functions outside both lists
+(``LIBM_ONLY``: gamma functions, cbrt, hypot, exp2) still compile, through libm /
+ocml, without the bit-equality guarantee; ``SympyProblem`` warns about them.
 
 Callback ABI (all arrays are flat ``double``):
 
@@ -257,6 +262,9 @@ class HipExprPrinter(C99CodePrinter):
         # keep integers exact but typed double so that 1/2 can never appear
         return "%d.0" % int(expr) if abs(int(expr)) < 2**53 else repr(float(expr))
 
+    def _print_Pi(self, expr):
+        return "3.141592653589793"          # (a literal: M_PI is not part of C99)
+
     def _print_Rational(self, expr):
         return "(%d.0/%d.0)" % (expr.p, expr.q)
 
@@ -312,6 +320,34 @@ class HipExprPrinter(C99CodePrinter):
 
     def _print_cosh(self, expr):
         return self._sa_call("cosh", expr)
+
+    # inverse trigonometric / hyperbolic functions, erf, erfc: csrc/sa_math_inv.h (MATH_INV_C below)
+    def _print_asin(self, expr):
+        return self._sa_call("asin", expr)
+
+    def _print_acos(self, expr):
+        return self._sa_call("acos", expr)
+
+    def _print_atan(self, expr):
+        return self._sa_call("atan", expr)
+
+    def _print_atan2(self, expr):
+        return self._sa_call("atan2", expr)
+
+    def _print_asinh(self, expr):
+        return self._sa_call("asinh", expr)
+
+    def _print_acosh(self, expr):
+        return self._sa_call("acosh", expr)
+
+    def _print_atanh(self, expr):
+        return self._sa_call("atanh", expr)
+
+    def _print_erf(self, expr):
+        return self._sa_call("erf", expr)
+
+    def _print_erfc(self, expr):
+        return self._sa_call("erfc", expr)
 
     # helper functions of the reference (lambdify.py:59-77, 275-340)
     def _print_logaddexp(self, expr):
@@ -978,24 +1014,50 @@ def generate_problem_source(
         "",
     ]
     uses_math = any(_MATH_CALL.search(part) for part in parts if part)
-    parts[6] = math_c() if uses_math else "/* (no transcendental function: csrc/sa_math.h not embedded) */"
+    uses_inv = any(_MATH_INV_CALL.search(part) for part in parts if part)
+    parts[6] = math_c() if uses_math or uses_inv else "/* (no transcendental function: csrc/sa_math.h not embedded) */"
+    if uses_inv:                # the second block builds on the first (sa_exp, sa_log1p, the bit helpers)
+        parts[6] += "\n" + math_inv_c()
     return "\n".join(parts)
 
 
 #: a call of one of the deterministic functions of csrc/sa_math.h in generated text
 _MATH_CALL = re.compile(r"\bsa_(exp|expm1|log|log1p|sin|cos|tan|tanh|sinh|cosh|pow|logaddexp|expit|dexpit|"
                         r"cardinal_bspline4)\(")
+#: ... and of csrc/sa_math_inv.h
+_MATH_INV_CALL = re.compile(r"\bsa_(asin|acos|atan|atan2|asinh|acosh|atanh|erf|erfc)\(")
 #: functions the C99 printer would hand to libm / ocml (not bit-reproducible between host and device)
-LIBM_ONLY = ("asin", "acos", "atan", "atan2", "asinh", "acosh", "atanh", "erf", "erfc", "tgamma", "lgamma", "cbrt",
-             "exp2", "log2", "log10", "hypot")
+LIBM_ONLY = ("tgamma", "lgamma", "cbrt", "exp2", "log2", "log10", "hypot")
+
+
+def _csrc(name: str) -> str:
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(os.path.dirname(here), "csrc", name)) as fh:
+        return fh.read()
 
 
 def math_c() -> str:
     """Text of csrc/sa_math.h (the deterministic exp / log / sin / pow ... shared by device and oracle)."""
-    import os
-    here = os.path.dirname(os.path.abspath(__file__))
-    with open(os.path.join(os.path.dirname(here), "csrc", "sa_math.h")) as fh:
-        return fh.read()
+    return _csrc("sa_math.h")
+
+
+def math_inv_c() -> str:
+    """Text of csrc/sa_math_inv.h (asin / acos / atan / atan2 / asinh / acosh / atanh / erf / erfc on the functions of
+    sa_math.h): embedded after ``math_c()`` in the headers that call one of them."""
+    return _csrc("sa_math_inv.h")
+
+
+def math_inv_boundaries() -> Dict[str, Tuple[float, ...]]:
+    """{function: the arguments at which its implementation changes interval}, read from the ``SAM_<FN>_B<k>``
+    definitions of csrc/sa_math_inv.h (erfc also changes where erf does above its own switch; atan2 changes where
+    atan does, in |y / x|)."""
+    found: Dict[str, List[float]] = {}
+    for fn, value in re.findall(r"^#define SAM_([A-Z0-9]+)_B\d+ +(\S+)", math_inv_c(), re.M):
+        found.setdefault(fn.lower(), []).append(float(value))
+    found["erfc"] = found["erfc"] + [v for v in found["erf"] if v > max(found["erfc"])]
+    found["atan2"] = list(found["atan"])
+    return {fn: tuple(sorted(v)) for fn, v in found.items()}
 
 
 def libm_calls(source: str) -> List[str]:

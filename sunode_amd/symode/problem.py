@@ -653,6 +653,12 @@ class SympyProblem:
                 description=desc, matvec=self._matvec, matfill=self._matfill,
                 leaf_axes=None if os.environ.get("SA_NO_LANE_FAMILIES") else self._leaf_axes(),
             )
+            libm = codegen.libm_calls(self._native_source)
+            if libm:
+                import warnings
+                warnings.warn("the generated callbacks call %s through libm (host) / ocml (device): the device's results "
+                              "are not guaranteed to equal a host run's bit for bit for this model"
+                              % ", ".join(libm), UserWarning, stacklevel=2)
         return self._native_source
 
     # ------------------------------------------------------------------
@@ -727,7 +733,19 @@ def _cardinal_bspline(degree, t):
     return basis[0]
 
 
+def _erf(x):
+    from scipy import special           # (numpy has neither; imported on first use)
+    return special.erf(x)
+
+
+def _erfc(x):
+    from scipy import special
+    return special.erfc(x)
+
+
 _HOST_HELPERS = {
+    "erf": _erf,
+    "erfc": _erfc,
     "logaddexp": _logaddexp,
     "expit": _expit,
     "dexpit": lambda x: _expit(x) * _expit(-x),

@@ -15,6 +15,7 @@ Independent oracles for the integrator half:
 
 Usage: python tools/make_golden_truth.py   (a few minutes; outputs are committed)
        python tools/make_golden_truth.py --times    (only truth_times_<name>.npz: see ``times_truth``)
+       python tools/make_golden_truth.py --inverse-erf    (only truth_probit_gate.npz: see ``inverse_erf_truth``)
 """
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ sys.path.insert(0, ROOT)
 from sunode_amd import SympyProblem  # noqa: E402
 from sunode_amd.symode.problem import HOST_FUNCTIONS  # noqa: E402
 from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, forcing_batch, logistic_switch_batch, lv_batch,  # noqa: E402
-                            misc_batch, robertson_batch, seir_batch)
+                            misc_batch, probit_gate_batch, robertson_batch, seir_batch)
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -121,6 +122,17 @@ def transcendental_truth():
         y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
         np.savez(os.path.join(GOLD, "truth_%s.npz" % name), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
                  tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
+
+
+def inverse_erf_truth():
+    """truth_probit_gate.npz: 16 draws of ``probit_gate`` (erf / erfc / asin / acos / atan / atan2 / asinh / acosh /
+    atanh in one right-hand side; the host functions are numpy's and scipy.special's erf / erfc -- nothing of
+    csrc/sa_math_inv.h is on this side)."""
+    prob = make("probit_gate")
+    d = probit_gate_batch(16)
+    y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
+    np.savez(os.path.join(GOLD, "truth_probit_gate.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
+             tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
 
 
 def sweep_truth():
@@ -282,6 +294,9 @@ def main():
     if "--sweep" in sys.argv:
         sweep_truth()
         return
+    if "--inverse-erf" in sys.argv:
+        inverse_erf_truth()
+        return
     # ---------------- DVODE statistics ----------------
     def lv_f(t, y, a, b, c, d):
         return [a * y[0] - b * y[0] * y[1], d * y[0] * y[1] - c * y[1]]
@@ -370,6 +385,7 @@ def main():
     np.savez(os.path.join(GOLD, "truth_seir.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
              tvals=d["tvals"], grads=g, y_out=y_out, grad_params=gp, grad_y0=gy0)
     transcendental_truth()
+    inverse_erf_truth()
     sweep_truth()
     print("done")
 

@@ -132,6 +132,42 @@ def mathfn_b(t, y, p):
                   sym.sinh(x[4]) - sym.cosh(a[4])]}
 
 
+def mathfn_c(t, y, p):
+    """One or two functions of csrc/sa_math_inv.h per output -- asin / acos / atan / atan2 -- with a product or a
+    quotient of a state and a differentiated parameter as the argument, so that every callback (right-hand side,
+    Jacobian, adjoint, quadrature, adjoint Jacobian) carries a derivative of every function; atan2 with the state in
+    either slot (a second argument of unknown sign: sympy keeps atan2 there)."""
+    import sympy as sym
+    x, a = y.x, p.a
+    return {"x": [sym.asin(a[0] * x[0]), sym.acos(x[1] / a[1]), sym.atan(a[2] * x[2]), sym.atan2(x[3], a[3]),
+                  sym.atan2(a[4], x[4] - 2) + sym.asin(x[4] / a[4])]}
+
+
+def mathfn_d(t, y, p):
+    """... asinh / acosh / atanh / erf / erfc."""
+    import sympy as sym
+    x, a = y.x, p.a
+    return {"x": [sym.asinh(a[0] * x[0]), sym.acosh(1 + a[1] * x[1]), sym.atanh(x[2] / a[2]), sym.erf(a[3] * x[3]),
+                  sym.erfc(x[4] / a[4]) + sym.erf(x[4])]}
+
+
+def probit_gate(t, y, p):
+    """A PyMC-shaped model on the inverse / error functions: an activity x in [0, 1] switched on by a probit gate of
+    the resource z (erf of a state and two differentiated parameters), limited by an arctangent saturation
+    (atan(s z)); the resource follows an asinh transform of the activity (asinh(g x)); the read-out c accumulates the
+    remaining functions on arguments the dynamics keep inside their domains (0 <= x <= 1, z >= 0) -- except
+    asin(b x / (1 + z)), which a large b drives beyond 1: a recoverable right-hand-side failure of that instance."""
+    import sympy as sym
+    x, z, c = y.x, y.z, y.c
+    gate = (1 + sym.erf(p.k * (z - p.x_half) / sym.sqrt(2))) / 2
+    return {
+        "x": p.r * gate * (1 - x) - p.m * x * sym.atan(p.s * z),
+        "z": sym.asinh(p.g * x) - p.d * z,
+        "c": (sym.asin(p.b * x / (1 + z)) + sym.acos(x / 2) * sym.atanh(z / (4 + z)) + sym.atan2(x, z - 1)
+              - sym.acosh(sym.Rational(3, 2) + x * z) + sym.erfc(z) - c / 5),
+    }
+
+
 def huge_pivots(t, y, p):
     """Decay rates of 1e200 on components that are exactly zero: the Newton matrix I - gamma*J has diagonal entries
     around 1e200 (beyond 2^500) while the steps stay of order 1 -- the pivots' reciprocals leave the range in which the
@@ -239,6 +275,14 @@ EXTRA_PROBLEMS = {
         states={"x": (), "v": ()},
         rhs=logistic_switch,
         derivative_params=[("log_r",), ("log_K",), ("k",), ("x_half",), ("q",)],
+    ),
+    "mathfn_c": dict(params={"a": (5,)}, states={"x": (5,)}, rhs=mathfn_c, derivative_params=[("a",)]),
+    "mathfn_d": dict(params={"a": (5,)}, states={"x": (5,)}, rhs=mathfn_d, derivative_params=[("a",)]),
+    "probit_gate": dict(
+        params={"k": (), "x_half": (), "s": (), "g": (), "b": (), "r": (), "m": (), "d": ()},
+        states={"x": (), "z": (), "c": ()},
+        rhs=probit_gate,
+        derivative_params=[("k",), ("x_half",), ("s",), ("g",), ("b",)],
     ),
     "sir2": dict(
         params={"beta": (2,), "C": (2, 2), "gamma": (), "pop": (2,)},
@@ -401,6 +445,17 @@ def logistic_switch_batch(B: int, seed: int = SEED, idx=None):
     tvals = np.linspace(0, 8, 9)
     return dict(ps=ps, pr=np.array([0.7]), y0=y0, tvals=tvals, t0=0.0,
                 grads=_cotangents(len(z), len(tvals), 2, idx), rtol=1e-8, atol=1e-8)
+
+
+def probit_gate_batch(B: int, seed: int = SEED, idx=None):
+    """Draws for ``probit_gate``: subset (k, x_half, s, g, b), remainder (r, m, d)."""
+    z = np.stack([std_normal(seed, 1280 + k, B, idx) for k in range(5)], axis=1)
+    ps = np.array([3.0, 0.6, 2.0, 1.5, 0.9]) * np.exp(0.1 * z)
+    zy = np.stack([std_normal(seed, 1290 + s, B, idx) for s in range(2)], axis=1)
+    y0 = np.concatenate([np.array([0.1, 0.2]) * np.exp(0.1 * zy), np.zeros((len(z), 1))], axis=1)
+    tvals = np.linspace(0, 8, 9)
+    return dict(ps=ps, pr=np.array([1.2, 0.8, 0.7]), y0=y0, tvals=tvals, t0=0.0,
+                grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
 
 
 def misc_batch(B: int, seed: int = SEED, idx=None):
