@@ -89,6 +89,45 @@ constexpr int sa_tau_c(int f, int j) { return j == 0 ? f : (j == f ? 0 : j); }
 #define SA_SEARCH_CACHE 0
 #endif
 #endif
+/* SA_INTERP_FAST (on for table records without Hermite: the two-state builds): fewer instructions and one wait less per
+   interpolation of the backward kernel, same arithmetic, same index, same counters:
+     SA_INTERP_FAST_MOVE   the move by ONE index to the left -- nearly every move there is -- as straight-line selects
+                           from tlo / tlo2, which are in registers; every other case (a move to the right, further to
+                           the left, to index 0 or 1, fresh data, t off either end) runs CVAfindIndex' walk as before,
+                           behind one wave-uniform branch;
+     SA_INTERP_FAST_TOUCH  the look-ahead touches of the next record are issued AFTER the evaluation has consumed the
+                           copied table: the memory counter retires in order, so touches issued between the record's
+                           loads make the copy wait for a record that is not in L2 (which is why it is touched);
+     SA_FWD_TOUT_REG       (forward kernel) the next output time stays in a register and is loaded when the output
+                           index advances, not after every completed step.
+   Each of the three has its own switch and follows SA_INTERP_FAST unless set; -DSA_INTERP_FAST=0 through
+   SA_KERNEL_DEFINES gives the text without them.  Same index, same results, same counters (tests/
+   test_interp_fast_move.py, tests/test_gpu_interp_fast.py).  The A/B of the whole and of every switch on its own, the
+   kernel times, the phase shares and the counters: profiles/interp_fast_ab.txt.
+   Compact-record and Hermite builds: all of it off, whatever is set (their index search and their touches are other
+   text: SA_SEARCH_CACHE remembers the right neighbour in the walk, the compact branch touches for itself). */
+#ifndef SA_INTERP_FAST
+#define SA_INTERP_FAST 1
+#endif
+#ifndef SA_INTERP_FAST_MOVE
+#define SA_INTERP_FAST_MOVE SA_INTERP_FAST
+#endif
+#ifndef SA_INTERP_FAST_TOUCH
+#define SA_INTERP_FAST_TOUCH SA_INTERP_FAST
+#endif
+#ifndef SA_FWD_TOUT_REG
+#define SA_FWD_TOUT_REG SA_INTERP_FAST
+#endif
+#if defined(SA_COMPACT_TRAJ) || defined(SA_HERMITE)
+#undef SA_INTERP_FAST
+#undef SA_INTERP_FAST_MOVE
+#undef SA_INTERP_FAST_TOUCH
+#undef SA_FWD_TOUT_REG
+#define SA_INTERP_FAST 0
+#define SA_INTERP_FAST_MOVE 0
+#define SA_INTERP_FAST_TOUCH 0
+#define SA_FWD_TOUT_REG 0
+#endif
 #if defined(SA_ABLATE_PROFILE) && defined(SA_INTERP_PROFILE)
 #define IPH(m, k) PHASE(m, k)
 #else
@@ -391,6 +430,22 @@ DEV int interp_y(Cv<BWD> &m, double t)
     INTERP_COUNT(m.n_interp);
     IPH(m, 0);
     int newpoint = 0, indx;
+#if SA_INTERP_FAST_MOVE
+    /* one index to the left: (t - tlo) < 0 takes the walk's first step, ilast >= 2 keeps it off index 0, and
+       !((t - tlo2) <= 0) is the comparison that ends the walk at its second look -- what the walk leaves behind,
+       without a loop and without a load (tests/test_interp_fast_move.py) */
+    const bool move1 = !m.newdata && (t - m.tlo) < 0.0 && m.ilast >= 2 && !((t - m.tlo2) <= 0.0);
+    const bool walk = m.newdata || (!move1 && ((t - m.tlo) < 0.0 || (t - m.thi) > 0.0));
+    {
+        const double tlo_old = m.tlo;
+        indx = m.ilast - (move1 ? 1 : 0);
+        m.ilast = indx;
+        m.thi = move1 ? tlo_old : m.thi;
+        m.tlo = move1 ? m.tlo2 : tlo_old;
+        newpoint = move1 ? 1 : 0;
+    }
+    if (wave_any(walk)) { if (walk) {
+#endif
     if (m.newdata) {
         m.ilast = m.np - 1; newpoint = 1; m.newdata = 0;
         m.tlo = point_time(m, m.ilast - 1); m.thi = point_time(m, m.ilast);
@@ -483,6 +538,9 @@ DEV int interp_y(Cv<BWD> &m, double t)
         m.tlo = tprev; m.thi = tcur;
         if ((t - m.thi) > FUZZ_FACTOR_ADJ * UROUND * (fabs(m.tfinal) + 1.0)) return CV_GETY_BADT;
     }
+#if SA_INTERP_FAST_MOVE
+    } }
+#endif
     m.have_last = 1;
     m.last_t = t;
     IPH(m, 1);
@@ -559,10 +617,12 @@ DEV int interp_y(Cv<BWD> &m, double t)
         }
 #else
         SFOR(f, 0, TREC) LT(m, f) = r[f]; SEND
+#if !SA_INTERP_FAST_TOUCH
         {   /* touch the record of the next index to the left so that it is L2-resident when needed */
             const double *rn = r - (indx > 0 ? m.trow : 0);
             m.pf[0] = rn[0]; m.pf[1] = rn[TREC / 3]; m.pf[2] = rn[2 * TREC / 3]; m.pf[3] = rn[TREC - 1];
         }
+#endif
 #endif
         if (LT(m, 0) > (double)indx) return CV_GETY_BADT;    /* CVODES would shift the base; cannot occur */
         if (indx == m.ilast) m.tlo2 = LT(m, 4);              /* T[2] = t[ilast-2] for the next move */
@@ -585,6 +645,17 @@ DEV int interp_y(Cv<BWD> &m, double t)
             m.ytmp[k] = acc;
         } SEND
     }
+#if SA_INTERP_FAST_TOUCH
+    if (newpoint) {
+        /* touch the record of the next index to the left so that it is L2-resident when needed -- after the
+           evaluation: the offset passes through an empty statement that reads the result, so the touches cannot be
+           issued among the record's own loads (an offset, not the pointer, which would lose its address space) */
+        int64_t off = (int64_t)(indx - (indx > 0 ? 1 : 0)) * m.trow;
+        asm volatile("" : "+v"(off) : "v"(m.ytmp[0]), "v"(m.ytmp[NS - 1]));
+        const double *rn = m.traj + off;
+        m.pf[0] = rn[0]; m.pf[1] = rn[TREC / 3]; m.pf[2] = rn[2 * TREC / 3]; m.pf[3] = rn[TREC - 1];
+    }
+#endif
     return CV_SUCCESS;
 }
 
@@ -984,8 +1055,16 @@ DEV void k_forward(const sa_fwd_args &a)
     bool done = (k >= a.n_t);
     StepCtl c;
     c.in_step = 0; c.redo = 0; c.nflag = FIRST_CALL; c.ncf = c.nef = c.nefQ = 0; c.convfail = 0; c.saved_t = SA_T0(a, inst);
+#if SA_FWD_TOUT_REG
+    double tout_k = done ? 0.0 : SA_TV(a, inst, k);      /* tvals[k], loaded again only when k advances */
+#define SA_TOUT_K(a, inst, k) tout_k
+#define SA_TOUT_NEXT(a, inst, k) do { if ((k) < (a).n_t) tout_k = SA_TV(a, inst, k); } while (0)
+#else
+#define SA_TOUT_K(a, inst, k) SA_TV(a, inst, k)
+#define SA_TOUT_NEXT(a, inst, k) do { } while (0)
+#endif
     if (!done) {
-        int flag = cv_first_call(m, SA_TV(a, inst, k));
+        int flag = cv_first_call(m, SA_TOUT_K(a, inst, k));
         if (flag != CV_SUCCESS) { status = flag; done = true; }
         else if (store) {
             hT[0] = m.tn;
@@ -1037,15 +1116,17 @@ DEV void k_forward(const sa_fwd_args &a)
                     }
                 }
                 while (!done && k < a.n_t) {
-                    double tout = SA_TV(a, inst, k);
+                    double tout = SA_TOUT_K(a, inst, k);
                     if (tout == SA_T0(a, inst)) {       /* (re-read: y0 is not worth NS register pairs across the whole loop) */
                         SFOR(i, 0, NS) yo[(int64_t)k * NS + i] = a.y0[(int64_t)inst * NS + i]; SEND
                         k++;
+                        SA_TOUT_NEXT(a, inst, k);
                     } else if ((m.tn - tout) * m.h >= 0.0) {
                         double dky[NSD], dq[NQD];
                         cv_get_dky0(m, tout, dky, dq);
                         SFOR(i, 0, NS) yo[(int64_t)k * NS + i] = dky[i]; SEND
                         k++;
+                        SA_TOUT_NEXT(a, inst, k);
                         nstloc = 0; retries = 0;
                     } else break;
                 }
@@ -1053,6 +1134,8 @@ DEV void k_forward(const sa_fwd_args &a)
             }
         }
     }
+#undef SA_TOUT_K
+#undef SA_TOUT_NEXT
     if (status != CV_SUCCESS) {
         for (int j = 0; j < a.n_t * NS; j++) yo[j] = SA_NAN;
     }
