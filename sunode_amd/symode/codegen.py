@@ -26,9 +26,12 @@ transcendental right-hand sides.  ``asin / acos / atan / atan2 / asinh / acosh /
 atanh / erf / erfc`` are printed the same way, as calls of ``csrc/sa_math_inv.h``:
 a second block, embedded after the first only when a callback calls one of its
 functions, so that the headers of models without them keep their text (and with
-it their cache keys and code objects).  Functions outside both lists
-(``LIBM_ONLY``: gamma functions, cbrt, hypot, exp2) still compile, through libm /
-ocml, without the bit-equality guarantee; ``SympyProblem`` warns about them.
+it their cache keys and code objects).  ``gamma / loggamma / digamma / trigamma``
+(``polygamma(0, .)``, ``polygamma(1, .)``, ``factorial``) are calls of a third block,
+``csrc/sa_math_gamma.h``, embedded after the others under the same rule;
+``polygamma(n, .)`` with n >= 2 has no implementation and raises.  Functions outside
+the three lists (``LIBM_ONLY``: cbrt, hypot, exp2, log2, log10) still compile, through
+libm / ocml, without the bit-equality guarantee; ``SympyProblem`` warns about them.
 
 Callback ABI (all arrays are flat ``double``):
 
@@ -348,6 +351,32 @@ class HipExprPrinter(C99CodePrinter):
 
     def _print_erfc(self, expr):
         return self._sa_call("erfc", expr)
+
+    # gamma family: csrc/sa_math_gamma.h (MATH_GAMMA_C below).  loggamma is printed as log|Gamma|, the real part:
+    # what C's lgamma and scipy.special.gammaln return
+    def _print_gamma(self, expr):
+        return self._sa_call("tgamma", expr)
+
+    def _print_loggamma(self, expr):
+        return self._sa_call("lgamma", expr)
+
+    def _print_digamma(self, expr):
+        return self._sa_call("digamma", expr)
+
+    def _print_trigamma(self, expr):
+        return self._sa_call("trigamma", expr)
+
+    def _print_polygamma(self, expr):
+        order, u = expr.args
+        if order == 0:
+            return "sa_digamma(%s)" % self._print(u)
+        if order == 1:
+            return "sa_trigamma(%s)" % self._print(u)
+        raise NotImplementedError("polygamma(%s, ...) has no deterministic implementation: derivatives up to the trigamma "
+                                  "function, polygamma(1, .), are supported (csrc/sa_math_gamma.h)" % order)
+
+    def _print_factorial(self, expr):
+        return "sa_tgamma(%s)" % self._print(expr.args[0] + 1)
 
     # helper functions of the reference (lambdify.py:59-77, 275-340)
     def _print_logaddexp(self, expr):
@@ -1015,9 +1044,13 @@ def generate_problem_source(
     ]
     uses_math = any(_MATH_CALL.search(part) for part in parts if part)
     uses_inv = any(_MATH_INV_CALL.search(part) for part in parts if part)
-    parts[6] = math_c() if uses_math or uses_inv else "/* (no transcendental function: csrc/sa_math.h not embedded) */"
+    uses_gamma = any(_MATH_GAMMA_CALL.search(part) for part in parts if part)
+    parts[6] = (math_c() if uses_math or uses_inv or uses_gamma
+                else "/* (no transcendental function: csrc/sa_math.h not embedded) */")
     if uses_inv:                # the second block builds on the first (sa_exp, sa_log1p, the bit helpers)
         parts[6] += "\n" + math_inv_c()
+    if uses_gamma:              # the third block builds on the first only (sa_exp, sa_log, the kernels of sa_log / sa_sin)
+        parts[6] += "\n" + math_gamma_c()
     return "\n".join(parts)
 
 
@@ -1026,8 +1059,10 @@ _MATH_CALL = re.compile(r"\bsa_(exp|expm1|log|log1p|sin|cos|tan|tanh|sinh|cosh|p
                         r"cardinal_bspline4)\(")
 #: ... and of csrc/sa_math_inv.h
 _MATH_INV_CALL = re.compile(r"\bsa_(asin|acos|atan|atan2|asinh|acosh|atanh|erf|erfc)\(")
+#: ... and of csrc/sa_math_gamma.h
+_MATH_GAMMA_CALL = re.compile(r"\bsa_(lgamma|tgamma|digamma|trigamma)\(")
 #: functions the C99 printer would hand to libm / ocml (not bit-reproducible between host and device)
-LIBM_ONLY = ("tgamma", "lgamma", "cbrt", "exp2", "log2", "log10", "hypot")
+LIBM_ONLY = ("cbrt", "exp2", "log2", "log10", "hypot")
 
 
 def _csrc(name: str) -> str:
@@ -1057,6 +1092,28 @@ def math_inv_boundaries() -> Dict[str, Tuple[float, ...]]:
         found.setdefault(fn.lower(), []).append(float(value))
     found["erfc"] = found["erfc"] + [v for v in found["erf"] if v > max(found["erfc"])]
     found["atan2"] = list(found["atan"])
+    return {fn: tuple(sorted(v)) for fn, v in found.items()}
+
+
+def math_gamma_c() -> str:
+    """Text of csrc/sa_math_gamma.h (lgamma / tgamma / digamma / trigamma on the functions of sa_math.h): embedded after
+    ``math_c()`` -- and after ``math_inv_c()`` where that is present -- in the headers that call one of them."""
+    return _csrc("sa_math_gamma.h")
+
+
+def math_gamma_boundaries() -> Dict[str, Tuple[float, ...]]:
+    """{function: the arguments y at which its implementation changes piece}, read from the ``SAM_<FN>_B<k>``
+    definitions of csrc/sa_math_gamma.h.  An argument below the first boundary is shifted up by one, so lgamma /
+    digamma / trigamma also change piece at ``b - 1`` for the boundaries b in (B1, B1 + 1]; tgamma's recurrence changes
+    its number of active stages at every integer up to its boundary."""
+    found: Dict[str, List[float]] = {}
+    for fn, value in re.findall(r"^#define SAM_([A-Z0-9]+)_B\d+ +(\S+)", math_gamma_c(), re.M):
+        found.setdefault(fn.lower(), []).append(float(value))
+    for fn in ("lgamma", "digamma", "trigamma"):
+        first = min(found[fn])
+        found[fn] += [b - 1.0 for b in found[fn] if first < b <= first + 1.0 and b - 1.0 > 0.0 and b - 1.0 not in found[fn]]
+    stages = int(re.search(r"^#define SAM_TGAMMA_STAGES +(\d+)", math_gamma_c(), re.M).group(1))
+    found["tgamma"] = [found["tgamma"][0] - k for k in range(stages)]
     return {fn: tuple(sorted(v)) for fn, v in found.items()}
 
 

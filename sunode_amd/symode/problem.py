@@ -743,9 +743,35 @@ def _erfc(x):
     return special.erfc(x)
 
 
+def _gamma(x):
+    from scipy import special
+    return special.gamma(x)
+
+
+def _loggamma(x):
+    from scipy import special           # (log|Gamma|, as the generated callbacks compute it)
+    return special.gammaln(x)
+
+
+def _polygamma(n, x):
+    from scipy import special
+    return special.digamma(x) if n == 0 else special.polygamma(n, x)
+
+
+def _factorial(x):
+    from scipy import special
+    return special.gamma(np.asarray(x, dtype=float) + 1.0)
+
+
 _HOST_HELPERS = {
     "erf": _erf,
     "erfc": _erfc,
+    "gamma": _gamma,
+    "loggamma": _loggamma,
+    "polygamma": _polygamma,
+    "digamma": lambda x: _polygamma(0, x),
+    "trigamma": lambda x: _polygamma(1, x),
+    "factorial": _factorial,
     "logaddexp": _logaddexp,
     "expit": _expit,
     "dexpit": lambda x: _expit(x) * _expit(-x),

@@ -16,6 +16,7 @@ Independent oracles for the integrator half:
 Usage: python tools/make_golden_truth.py   (a few minutes; outputs are committed)
        python tools/make_golden_truth.py --times    (only truth_times_<name>.npz: see ``times_truth``)
        python tools/make_golden_truth.py --inverse-erf    (only truth_probit_gate.npz: see ``inverse_erf_truth``)
+       python tools/make_golden_truth.py --gamma    (only truth_gamma_delay.npz: see ``gamma_truth``)
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ sys.path.insert(0, ROOT)
 from sunode_amd import SympyProblem  # noqa: E402
 from sunode_amd.symode.problem import HOST_FUNCTIONS  # noqa: E402
 from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, forcing_batch, logistic_switch_batch, lv_batch,  # noqa: E402
-                            misc_batch, probit_gate_batch, robertson_batch, seir_batch)
+                            gamma_delay_batch, misc_batch, probit_gate_batch, robertson_batch, seir_batch)
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -132,6 +133,17 @@ def inverse_erf_truth():
     d = probit_gate_batch(16)
     y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
     np.savez(os.path.join(GOLD, "truth_probit_gate.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
+             tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
+
+
+def gamma_truth():
+    """truth_gamma_delay.npz: 16 draws of ``gamma_delay`` (loggamma / gamma / digamma of states and of the inferred
+    shape; their derivatives through polygamma; the host functions are scipy.special's gammaln / gamma / digamma /
+    polygamma -- nothing of csrc/sa_math_gamma.h is on this side)."""
+    prob = make("gamma_delay")
+    d = gamma_delay_batch(16)
+    y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
+    np.savez(os.path.join(GOLD, "truth_gamma_delay.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
              tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
 
 
@@ -297,6 +309,9 @@ def main():
     if "--inverse-erf" in sys.argv:
         inverse_erf_truth()
         return
+    if "--gamma" in sys.argv:
+        gamma_truth()
+        return
     # ---------------- DVODE statistics ----------------
     def lv_f(t, y, a, b, c, d):
         return [a * y[0] - b * y[0] * y[1], d * y[0] * y[1] - c * y[1]]
@@ -386,6 +401,7 @@ def main():
              tvals=d["tvals"], grads=g, y_out=y_out, grad_params=gp, grad_y0=gy0)
     transcendental_truth()
     inverse_erf_truth()
+    gamma_truth()
     sweep_truth()
     print("done")
 

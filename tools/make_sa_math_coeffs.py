@@ -1,12 +1,14 @@
-"""Coefficients of sunode_amd/csrc/sa_math_inv.h (inverse trigonometric / hyperbolic functions, erf, erfc).
+"""Coefficients of sunode_amd/csrc/sa_math_inv.h (inverse trigonometric / hyperbolic functions, erf, erfc) and of
+sunode_amd/csrc/sa_math_gamma.h (lgamma, tgamma, digamma, trigamma).
 
 Every polynomial of that header is a Chebyshev-node interpolant (near-minimax) computed here with mpmath at 120
 digits, converted to the monomial basis of the header's own variable, rounded to double and then MEASURED: the
 error of the rounded polynomial against the function, in exact arithmetic, over 1 001 points of the fit
 interval.  Nothing is transcribed from another library.
 
-    python tools/make_sa_math_coeffs.py            # prints the literal blocks the header carries
-    python tools/make_sa_math_coeffs.py --check    # compares them with the header's text (exit status 1 on a difference)
+    python tools/make_sa_math_coeffs.py            # prints the literal blocks the headers carry
+    python tools/make_sa_math_coeffs.py --check    # compares them with the headers' text (exit status 1 on a difference)
+    python tools/make_sa_math_coeffs.py --gamma    # (with either form) only sa_math_gamma.h; --inv: only sa_math_inv.h
 
 Sets (variable, interval, form):
 
@@ -17,6 +19,18 @@ Sets (variable, interval, form):
             piece i   X_i(w) = erfcx(c_i + w),  |w| <= h_i          (argument pieces, a = |x| in [c_i - h_i, c_i + h_i])
             piece j   A_j(w) = a erfcx(a), a = (u_j + w)^(-1/2)     (asymptotic pieces in u = 1/a^2)
           erfcx(a) = exp(a^2) erfc(a).
+
+sa_math_gamma.h: one Horner chain per function, coefficients selected among four pieces (y: the argument, after the
+shift x + 1 of a small one or the reflection 1 - x / -x of a negative one):
+
+  LGAMMA    pieces 0-2  G(w) = lgamma(y) / ((y - 1)(y - 2)),  y = c_i + w in [3/4, 3/2], [3/2, 3], [3, 6]
+            piece 3     S(w) = y (lgamma(y) - (y - 1/2) ln y + y - ln(2 pi)/2),  w = 1/y^2 in [0, 1/36]
+                        (also the exponent of tgamma, whose argument an upward recurrence lifts to y >= 6)
+  DIGAMMA   piece 0     psi(y) / (y - x0),  y = c_0 + w in [1, 2]  (x0: the positive root, carried in two words)
+            pieces 1-2  psi(y),  y = c_i + w in [2, 4], [4, 8]
+            piece 3     D(w) = (ln y - 1/(2y) - psi(y)) / w,  w = 1/y^2 in [0, 1/64]
+  TRIGAMMA  pieces 0-2  psi'(y),  y = c_i + w in [1, 2], [2, 4], [4, 8]
+            piece 3     T(w) = (y psi'(y) - 1 - 1/(2y)) / w,  w = 1/y^2 in [0, 1/64]
 """
 from __future__ import annotations
 
@@ -28,6 +42,7 @@ import mpmath as mp
 
 mp.mp.dps = 120
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sunode_amd", "csrc", "sa_math_inv.h")
+HEADER_GAMMA = os.path.join(os.path.dirname(HEADER), "sa_math_gamma.h")
 
 #: interval boundaries of atan's argument reduction (|x|): the header's SAM_ATAN_B1..4; the reduced argument is
 #: largest, 7/16, at the upper end of the first interval
@@ -39,6 +54,11 @@ ERF_BOUNDS = ("1.0", "1.5", "2.5", "4.0", "8.0")
 ERFC_DIRECT = "0.5"
 #: beyond this erfc underflows to zero (exp(-27.3^2) < 2^-1075): the argument is clamped here (SAM_ERFC_CLAMP)
 ERFC_CLAMP = "27.5"
+#: sa_math_gamma.h: boundaries of the pieces in y (SAM_LGAMMA_B1..4, SAM_DIGAMMA_B1..4, SAM_TRIGAMMA_B1..4); below the
+#: first one the argument is shifted by one (lgamma x = lgamma(x + 1) - ln x, psi x = psi(x + 1) - 1/x, ...)
+LGAMMA_BOUNDS = ("0.75", "1.5", "3.0", "6.0")
+DIGAMMA_BOUNDS = ("1.0", "2.0", "4.0", "8.0")
+TRIGAMMA_BOUNDS = ("1.0", "2.0", "4.0", "8.0")
 #: error asked of every fit before its coefficients are rounded (relative to the quantity the header forms from it):
 #: the rounding of the leading coefficient alone is up to 2^-54, the evaluation's roundings more
 TARGET = mp.mpf(2) ** -58
@@ -182,30 +202,158 @@ def blocks():
     return out
 
 
-def main():
-    text = blocks()
-    if "--check" in sys.argv:
-        with open(HEADER) as fh:
-            hdr = fh.read()
-        bad = 0
-        want = {"SAM_ATAN_B%d" % (k + 1): v for k, v in enumerate(ATAN_BOUNDS)}
-        want.update({"SAM_ERF_B%d" % (k + 1): v for k, v in enumerate(ERF_BOUNDS)})
-        want.update({"SAM_ERFC_B1": ERFC_DIRECT, "SAM_ERFC_CLAMP": ERFC_CLAMP})
-        for macro, value in want.items():               # the boundaries the fits were made for
-            m = re.search(r"^#define %s +(\S+)" % macro, hdr, re.M)
-            if m is None or float(m.group(1)) != float(value):
-                print("%s of %s is not %s" % (macro, HEADER, value))
-                bad = 1
-        for name, lines in text.items():
-            m = re.search(r"/\* BEGIN GENERATED %s[^\n]*\n(.*?)\n[^\n]*END GENERATED %s" % (name, name), hdr, re.S)
-            if m is None or m.group(1).strip() != "\n".join(lines).strip():
-                print("block %s of %s differs from the generator's output" % (name, HEADER))
-                bad = 1
-        sys.exit(bad)
+# ---- sa_math_gamma.h ----
+def psi_root():
+    return mp.findroot(lambda v: mp.psi(0, v), mp.mpf("1.4616321449683623"))
+
+
+def f_lgamma(y):
+    """lgamma(y) / ((y - 1)(y - 2)): gamma_E at 1 and 1 - gamma_E at 2"""
+    d = (y - 1) * (y - 2)
+    if abs(d) < mp.mpf(10) ** -60:
+        return mp.euler if abs(y - 1) < 0.5 else 1 - mp.euler
+    return mp.loggamma(y) / d
+
+
+def f_stirling(w):
+    if w == 0:
+        return mp.mpf(1) / 12
+    y = 1 / mp.sqrt(w)
+    return y * (mp.loggamma(y) - (y - mp.mpf(1) / 2) * mp.log(y) + y - mp.log(2 * mp.pi) / 2)
+
+
+def f_digamma0(y):
+    x0 = psi_root()
+    if abs(y - x0) < mp.mpf(10) ** -60:
+        return mp.psi(1, x0)
+    return mp.psi(0, y) / (y - x0)
+
+
+def f_digamma_asym(w):
+    if w == 0:
+        return mp.mpf(1) / 12
+    y = 1 / mp.sqrt(w)
+    return (mp.log(y) - 1 / (2 * y) - mp.psi(0, y)) / w
+
+
+def f_trigamma_asym(w):
+    if w == 0:
+        return mp.mpf(1) / 6
+    y = 1 / mp.sqrt(w)
+    return (y * mp.psi(1, y) - 1 - 1 / (2 * y)) / w
+
+
+def chain(name, pieces):
+    """One Horner chain SAM_<NAME>_HORNER(p, w) whose coefficients SAM_<NAME>_SEL picks among the pieces, and the
+    centres SAM_<NAME>_C<i> of the pieces fitted in y - c.  pieces: (text, coefficients low..high, centre or None)"""
+    deg = max(len(p[1]) for p in pieces) - 1
+    lines = ["    /* coefficients by piece (zero above a piece's own degree); one Horner chain of degree %d" % deg]
+    lines += ["       %s" % p[0] for p in pieces]
+    lines[-1] += " */"
+    for k, p in enumerate(pieces):
+        if p[2] is not None:
+            lines.append("#define SAM_%s_C%d %s" % (name, k, lit(p[2])))
+
+    def sel(j):
+        return "SAM_%s_SEL(%s)" % (name, ", ".join(lit(p[1][j]) if j < len(p[1]) else "0.0" for p in pieces))
+    lines.append("#define SAM_%s_HORNER(p, w) \\" % name)
+    lines.append("    p = %s; \\" % sel(deg))
+    for j in range(deg - 1, -1, -1):
+        lines.append("    p = fma(p, w, %s);%s" % (sel(j), " \\" if j else ""))
+    return lines
+
+
+def gamma_blocks():
+    out = {}
+    lines = []
+    for name, value in (("GPI", mp.pi), ("GPISQ", mp.pi ** 2), ("HLN2PI", mp.log(2 * mp.pi) / 2), ("PSI_X0", psi_root())):
+        hi, lo = hi_lo(value)
+        lines += ["#define SAM_%s_HI %s" % (name, hi), "#define SAM_%s_LO %s" % (name, lo)]
+    # the largest doubles whose result is below 2^1024, by bisection
+    def last_below(f, lo, hi):
+        lo, hi = mp.mpf(lo), mp.mpf(hi)
+        for _ in range(160):
+            mid = (lo + hi) / 2
+            lo, hi = (mid, hi) if f(mid) < mp.mpf(2) ** 1024 else (lo, mid)
+        v = float(lo)
+        return v if mp.mpf(v) <= lo else float(mp.mpf(v) * (1 - mp.mpf(2) ** -53))
+    lines.append("#define SAM_TGAMMA_MAX %s" % lit(last_below(mp.gamma, 171, 172)))
+    lines.append("#define SAM_LGAMMA_MAX %s" % lit(last_below(mp.loggamma, "2e305", "3e305")))
+    out["CONST"] = lines
+
+    def pieces_of(bounds, fs, tag):
+        b = [mp.mpf(v) for v in bounds]
+        ps = []
+        for k, f in enumerate(fs):
+            ck, err, cen = fit(f, b[k], b[k + 1], centred=True, nmin=14, nmax=44)
+            ps.append(("piece %d: %s, y = c + w, c = %s, y in [%s, %s]: degree %d, error 2^%.1f"
+                       % (k, tag[k], lit(cen), lit(b[k]), lit(b[k + 1]), len(ck) - 1, float(mp.log(err, 2))), ck, cen))
+        return ps
+
+    def asym(f, b, weight, text):
+        hi = 1 / mp.mpf(b) ** 2
+        ck, err, _ = fit(f, 0, hi, weight=weight, nmin=5)
+        return ("piece 3: %s, w = 1/y^2 in [0, %s]: degree %d, error 2^%.1f (of the function's value)"
+                % (text, lit(hi), len(ck) - 1, float(mp.log(err, 2))), ck, None)
+
+    def yw(w):
+        return 1 / mp.sqrt(w)
+    g = "G = lgamma(y)/((y - 1)(y - 2))"
+    ps = pieces_of(LGAMMA_BOUNDS, [f_lgamma] * 3, [g] * 3)
+    ps.append(asym(f_stirling, LGAMMA_BOUNDS[3], lambda w: mp.loggamma(yw(w)) * yw(w) if w != 0 else mp.mpf(0),
+                   "S = y (lgamma(y) - (y - 1/2) ln y + y - ln(2 pi)/2)"))
+    out["LGAMMA"] = chain("LGAMMA", ps)
+    ps = pieces_of(DIGAMMA_BOUNDS, [f_digamma0, lambda v: mp.psi(0, v), lambda v: mp.psi(0, v)],
+                   ["psi(y)/(y - x0)", "psi(y)", "psi(y)"])
+    ps.append(asym(f_digamma_asym, DIGAMMA_BOUNDS[3], lambda w: mp.psi(0, yw(w)) / w if w != 0 else mp.mpf(0),
+                   "D = (ln y - 1/(2y) - psi(y))/w"))
+    out["DIGAMMA"] = chain("DIGAMMA", ps)
+    ps = pieces_of(TRIGAMMA_BOUNDS, [lambda v: mp.psi(1, v)] * 3, ["psi'(y)"] * 3)
+    ps.append(asym(f_trigamma_asym, TRIGAMMA_BOUNDS[3], lambda w: yw(w) * mp.psi(1, yw(w)) / w if w != 0 else mp.mpf(0),
+                   "T = (y psi'(y) - 1 - 1/(2y))/w"))
+    out["TRIGAMMA"] = chain("TRIGAMMA", ps)
+    return out
+
+
+def check(header, text, want):
+    with open(header) as fh:
+        hdr = fh.read()
+    bad = 0
+    for macro, value in want.items():               # the boundaries the fits were made for
+        m = re.search(r"^#define %s +(\S+)" % macro, hdr, re.M)
+        if m is None or float(m.group(1)) != float(value):
+            print("%s of %s is not %s" % (macro, header, value))
+            bad = 1
     for name, lines in text.items():
-        print("/* BEGIN GENERATED %s (tools/make_sa_math_coeffs.py) */" % name)
-        print("\n".join(lines))
-        print("/* END GENERATED %s */" % name)
+        m = re.search(r"/\* BEGIN GENERATED %s[^\n]*\n(.*?)\n[^\n]*END GENERATED %s" % (name, name), hdr, re.S)
+        if m is None or m.group(1).strip() != "\n".join(lines).strip():
+            print("block %s of %s differs from the generator's output" % (name, header))
+            bad = 1
+    return bad
+
+
+def main():
+    which = [w for w in ("inv", "gamma") if "--" + w in sys.argv] or ["inv", "gamma"]
+    bad = 0
+    for w in which:
+        text = blocks() if w == "inv" else gamma_blocks()
+        if "--check" in sys.argv:
+            if w == "inv":
+                want = {"SAM_ATAN_B%d" % (k + 1): v for k, v in enumerate(ATAN_BOUNDS)}
+                want.update({"SAM_ERF_B%d" % (k + 1): v for k, v in enumerate(ERF_BOUNDS)})
+                want.update({"SAM_ERFC_B1": ERFC_DIRECT, "SAM_ERFC_CLAMP": ERFC_CLAMP})
+                bad |= check(HEADER, text, want)
+            else:
+                want = {"SAM_%s_B%d" % (fn, k + 1): v for fn, bs in (("LGAMMA", LGAMMA_BOUNDS), ("DIGAMMA", DIGAMMA_BOUNDS),
+                                                                      ("TRIGAMMA", TRIGAMMA_BOUNDS)) for k, v in enumerate(bs)}
+                bad |= check(HEADER_GAMMA, text, want)
+            continue
+        for name, lines in text.items():
+            print("/* BEGIN GENERATED %s (tools/make_sa_math_coeffs.py) */" % name)
+            print("\n".join(lines))
+            print("/* END GENERATED %s */" % name)
+    if "--check" in sys.argv:
+        sys.exit(bad)
 
 
 if __name__ == "__main__":

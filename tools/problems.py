@@ -168,6 +168,36 @@ def probit_gate(t, y, p):
     }
 
 
+def mathfn_e(t, y, p):
+    """One or two functions of csrc/sa_math_gamma.h per output -- loggamma (log|Gamma|) / gamma / digamma / factorial --
+    with a product or a quotient of a state and a differentiated parameter as the argument.  The derivatives bring
+    Gamma psi, psi and psi' into the Jacobian, the adjoint and the quadrature; the trigamma function is reachable ONLY
+    as the derivative of digamma(a x).  The arguments of output 3 cross zero and the negative axis with the sign of
+    x[3]; output 4 has the form 1 + a x (factorial(u) = Gamma(u + 1))."""
+    import sympy as sym
+    x, a = y.x, p.a
+    return {"x": [sym.loggamma(a[0] * x[0]), sym.gamma(x[1] / a[1]), sym.digamma(a[2] * x[2]),
+                  sym.loggamma(a[3] * x[3]) + sym.digamma(x[3] / a[3]), sym.factorial(a[4] * x[4])]}
+
+
+def gamma_delay(t, y, p):
+    """A PyMC-shaped model on the gamma family: the pool x is fed through a gamma-distributed delay -- the forcing is
+    the gamma density of t + tau with an inferred shape k and scale theta, written with loggamma(k), so the quadrature
+    carries psi(k) --, loses mass at rate m and gains e Gamma(1 - b x): harmless while b x stays small, a finite-time
+    blow-up into the pole of Gamma at b x = 1 when b alone is raised (a per-instance solver failure).  The response
+    z follows g x against a loggamma(2 + z) loss; the read-out c accumulates digamma(1 + x + z).  Jacobian, adjoint and
+    adjoint Jacobian carry Gamma psi, psi and psi'."""
+    import sympy as sym
+    x, z, c = y.x, y.z, y.c
+    u = (t + p.tau) / p.theta
+    density = sym.exp((p.k - 1) * sym.log(u) - u - sym.loggamma(p.k)) / p.theta
+    return {
+        "x": p.A * density - p.m * x + p.e * sym.gamma(1 - p.b * x),
+        "z": p.g * x - p.d * sym.loggamma(2 + z),
+        "c": sym.digamma(1 + x + z) - c / 5,
+    }
+
+
 def huge_pivots(t, y, p):
     """Decay rates of 1e200 on components that are exactly zero: the Newton matrix I - gamma*J has diagonal entries
     around 1e200 (beyond 2^500) while the steps stay of order 1 -- the pivots' reciprocals leave the range in which the
@@ -283,6 +313,13 @@ EXTRA_PROBLEMS = {
         states={"x": (), "z": (), "c": ()},
         rhs=probit_gate,
         derivative_params=[("k",), ("x_half",), ("s",), ("g",), ("b",)],
+    ),
+    "mathfn_e": dict(params={"a": (5,)}, states={"x": (5,)}, rhs=mathfn_e, derivative_params=[("a",)]),
+    "gamma_delay": dict(
+        params={"k": (), "theta": (), "b": (), "g": (), "A": (), "tau": (), "m": (), "e": (), "d": ()},
+        states={"x": (), "z": (), "c": ()},
+        rhs=gamma_delay,
+        derivative_params=[("k",), ("theta",), ("b",), ("g",), ("A",)],
     ),
     "sir2": dict(
         params={"beta": (2,), "C": (2, 2), "gamma": (), "pop": (2,)},
@@ -455,6 +492,17 @@ def probit_gate_batch(B: int, seed: int = SEED, idx=None):
     y0 = np.concatenate([np.array([0.1, 0.2]) * np.exp(0.1 * zy), np.zeros((len(z), 1))], axis=1)
     tvals = np.linspace(0, 8, 9)
     return dict(ps=ps, pr=np.array([1.2, 0.8, 0.7]), y0=y0, tvals=tvals, t0=0.0,
+                grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
+
+
+def gamma_delay_batch(B: int, seed: int = SEED, idx=None):
+    """Draws for ``gamma_delay``: subset (k, theta, b, g, A), remainder (tau, m, e, d)."""
+    z = np.stack([std_normal(seed, 1300 + k, B, idx) for k in range(5)], axis=1)
+    ps = np.array([3.0, 1.2, 0.5, 1.0, 2.0]) * np.exp(0.1 * z)
+    zy = np.stack([std_normal(seed, 1310 + s, B, idx) for s in range(2)], axis=1)
+    y0 = np.concatenate([np.array([0.1, 0.2]) * np.exp(0.1 * zy), np.zeros((len(z), 1))], axis=1)
+    tvals = np.linspace(0, 8, 9)
+    return dict(ps=ps, pr=np.array([0.5, 0.6, 0.05, 0.4]), y0=y0, tvals=tvals, t0=0.0,
                 grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
 
 

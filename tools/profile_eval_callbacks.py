@@ -4,7 +4,8 @@
     python tools/rocpd_summary.py <dir>/.../*_results.db
 
 ``mathfn_a`` (exp / log / log1p / expm1 / pow) is the yardstick the inverse / erf problems ``mathfn_c`` (asin / acos /
-atan / atan2) and ``mathfn_d`` (asinh / acosh / atanh / erf / erfc) are compared with: five outputs of one or two
+atan / atan2), ``mathfn_d`` (asinh / acosh / atanh / erf / erfc) and the gamma-family problem ``mathfn_e`` (loggamma /
+gamma / digamma / trigamma) are compared with: five outputs of one or two
 function calls each, plus their derivatives in the four other callbacks.  Arguments are drawn inside the domains (the
 main paths are branch-free: their cost does not depend on the interval).  Prints the host-side wall time per call (it
 includes the copies of 26 N doubles each way; the kernel time is the profiler's) and the registers / spill slots /
@@ -43,6 +44,8 @@ def main():
         par = rng.uniform(1.02, 1.1, (N, 5))
         if name == "mathfn_d":
             y[:, 3:] = rng.uniform(0.05, 20.0, (N, 2))         # erf / erfc: all pieces
+        if name == "mathfn_e":
+            y = rng.uniform(0.05, 20.0, (N, 5))                 # all pieces of the positive axis (no reflection)
     lam, t = rng.randn(N, 5), rng.uniform(0, 50, N)
     eng = Solver(prob)._engine()
     for k in range(repeats + 1):                               # (the first call loads the code object)
