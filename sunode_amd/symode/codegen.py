@@ -29,8 +29,11 @@ functions, so that the headers of models without them keep their text (and with
 it their cache keys and code objects).  ``gamma / loggamma / digamma / trigamma``
 (``polygamma(0, .)``, ``polygamma(1, .)``, ``factorial``) are calls of a third block,
 ``csrc/sa_math_gamma.h``, embedded after the others under the same rule;
-``polygamma(n, .)`` with n >= 2 has no implementation and raises.  Functions outside
-the three lists (``LIBM_ONLY``: cbrt, hypot, exp2, log2, log10) still compile, through
+``polygamma(n, .)`` with n >= 2 has no implementation and raises.  ``besselj / bessely /
+besseli / besselk`` of an integer literal order 0 ... ``SAM_BESSEL_NMAX`` are calls of a
+fourth block, ``csrc/sa_math_bessel.h`` (``sa_bessel_j(n, x)`` ...), embedded last under
+the same rule; a non-integer, symbolic or larger order raises.  Functions outside
+the four lists (``LIBM_ONLY``: cbrt, hypot, exp2, log2, log10) still compile, through
 libm / ocml, without the bit-equality guarantee; ``SympyProblem`` warns about them.
 
 Callback ABI (all arrays are flat ``double``):
@@ -377,6 +380,33 @@ class HipExprPrinter(C99CodePrinter):
 
     def _print_factorial(self, expr):
         return "sa_tgamma(%s)" % self._print(expr.args[0] + 1)
+
+    # Bessel functions of integer order: csrc/sa_math_bessel.h (MATH_BESSEL_C below).  The order is printed as an
+    # integer literal; sympy folds a negative integer order into a positive one itself, what is left of one goes
+    # through J_-n = (-1)^n J_n, Y_-n = (-1)^n Y_n, I_-n = I_n, K_-n = K_n
+    def _bessel_call(self, letter, expr, alternates):
+        order, u = expr.args
+        limit = math_bessel_nmax()
+        if not (order.is_Integer and abs(int(order)) <= limit):
+            raise NotImplementedError(
+                "bessel%s(%s, ...) has no deterministic implementation: the order must be an integer literal with "
+                "|order| <= SAM_BESSEL_NMAX = %d (csrc/sa_math_bessel.h); non-integer and symbolic orders are not supported"
+                % (letter, order, limit))
+        n = int(order)
+        call = "sa_bessel_%s(%d, %s)" % (letter, abs(n), self._print(u))
+        return "(-%s)" % call if (alternates and n < 0 and n % 2) else call
+
+    def _print_besselj(self, expr):
+        return self._bessel_call("j", expr, True)
+
+    def _print_bessely(self, expr):
+        return self._bessel_call("y", expr, True)
+
+    def _print_besseli(self, expr):
+        return self._bessel_call("i", expr, False)
+
+    def _print_besselk(self, expr):
+        return self._bessel_call("k", expr, False)
 
     # helper functions of the reference (lambdify.py:59-77, 275-340)
     def _print_logaddexp(self, expr):
@@ -1045,12 +1075,15 @@ def generate_problem_source(
     uses_math = any(_MATH_CALL.search(part) for part in parts if part)
     uses_inv = any(_MATH_INV_CALL.search(part) for part in parts if part)
     uses_gamma = any(_MATH_GAMMA_CALL.search(part) for part in parts if part)
-    parts[6] = (math_c() if uses_math or uses_inv or uses_gamma
+    uses_bessel = any(_MATH_BESSEL_CALL.search(part) for part in parts if part)
+    parts[6] = (math_c() if uses_math or uses_inv or uses_gamma or uses_bessel
                 else "/* (no transcendental function: csrc/sa_math.h not embedded) */")
     if uses_inv:                # the second block builds on the first (sa_exp, sa_log1p, the bit helpers)
         parts[6] += "\n" + math_inv_c()
     if uses_gamma:              # the third block builds on the first only (sa_exp, sa_log, the kernels of sa_log / sa_sin)
         parts[6] += "\n" + math_gamma_c()
+    if uses_bessel:             # the fourth block builds on the first only (sa_exp, sa_log, the kernels of sa_sin)
+        parts[6] += "\n" + math_bessel_c()
     return "\n".join(parts)
 
 
@@ -1061,6 +1094,8 @@ _MATH_CALL = re.compile(r"\bsa_(exp|expm1|log|log1p|sin|cos|tan|tanh|sinh|cosh|p
 _MATH_INV_CALL = re.compile(r"\bsa_(asin|acos|atan|atan2|asinh|acosh|atanh|erf|erfc)\(")
 #: ... and of csrc/sa_math_gamma.h
 _MATH_GAMMA_CALL = re.compile(r"\bsa_(lgamma|tgamma|digamma|trigamma)\(")
+#: ... and of csrc/sa_math_bessel.h
+_MATH_BESSEL_CALL = re.compile(r"\bsa_bessel_(j|y|i|k)\(")
 #: functions the C99 printer would hand to libm / ocml (not bit-reproducible between host and device)
 LIBM_ONLY = ("cbrt", "exp2", "log2", "log10", "hypot")
 
@@ -1114,6 +1149,31 @@ def math_gamma_boundaries() -> Dict[str, Tuple[float, ...]]:
         found[fn] += [b - 1.0 for b in found[fn] if first < b <= first + 1.0 and b - 1.0 > 0.0 and b - 1.0 not in found[fn]]
     stages = int(re.search(r"^#define SAM_TGAMMA_STAGES +(\d+)", math_gamma_c(), re.M).group(1))
     found["tgamma"] = [found["tgamma"][0] - k for k in range(stages)]
+    return {fn: tuple(sorted(v)) for fn, v in found.items()}
+
+
+def math_bessel_c() -> str:
+    """Text of csrc/sa_math_bessel.h (J_n / Y_n / I_n / K_n of integer order on the functions of sa_math.h): embedded
+    after the other blocks in the headers that call one of them."""
+    return _csrc("sa_math_bessel.h")
+
+
+def math_bessel_nmax() -> int:
+    """The largest order csrc/sa_math_bessel.h implements (its ``SAM_BESSEL_NMAX``)."""
+    return int(re.search(r"^#define SAM_BESSEL_NMAX +(\d+)", math_bessel_c(), re.M).group(1))
+
+
+def math_bessel_boundaries() -> Dict[str, Tuple[float, ...]]:
+    """{function: the arguments |x| at which its implementation changes piece}, read from the ``SAM_<FN>_B<k>``
+    definitions of csrc/sa_math_bessel.h: ``j0, j1, y0, y1, i0, i1, k0, k1`` (the orders 0 and 1) and ``jn, in`` (where
+    an order >= 2 of J / I changes method; J_n also changes the direction of its recurrence at |x| = n, and I above
+    ``SAM_I_FAR`` takes the exponential in two factors: that value is added to ``i0, i1, in``)."""
+    found: Dict[str, List[float]] = {}
+    for fn, value in re.findall(r"^#define SAM_([A-Z0-9]+)_B\d+ +(\S+)", math_bessel_c(), re.M):
+        found.setdefault(fn.lower(), []).append(float(value))
+    far = float(re.search(r"^#define SAM_I_FAR +(\S+)", math_bessel_c(), re.M).group(1))
+    for fn in ("i0", "i1", "in"):
+        found[fn].append(far)
     return {fn: tuple(sorted(v)) for fn, v in found.items()}
 
 

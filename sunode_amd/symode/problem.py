@@ -763,7 +763,18 @@ def _factorial(x):
     return special.gamma(np.asarray(x, dtype=float) + 1.0)
 
 
+def _bessel(kind):
+    def fn(n, x):
+        from scipy import special
+        return getattr(special, kind)(n, x)
+    return fn
+
+
 _HOST_HELPERS = {
+    "besselj": _bessel("jv"),
+    "bessely": _bessel("yv"),
+    "besseli": _bessel("iv"),
+    "besselk": _bessel("kv"),
     "erf": _erf,
     "erfc": _erfc,
     "gamma": _gamma,

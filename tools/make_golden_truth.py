@@ -17,6 +17,7 @@ Usage: python tools/make_golden_truth.py   (a few minutes; outputs are committed
        python tools/make_golden_truth.py --times    (only truth_times_<name>.npz: see ``times_truth``)
        python tools/make_golden_truth.py --inverse-erf    (only truth_probit_gate.npz: see ``inverse_erf_truth``)
        python tools/make_golden_truth.py --gamma    (only truth_gamma_delay.npz: see ``gamma_truth``)
+       python tools/make_golden_truth.py --bessel    (only truth_bessel_ring.npz: see ``bessel_truth``)
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 from sunode_amd import SympyProblem  # noqa: E402
 from sunode_amd.symode.problem import HOST_FUNCTIONS  # noqa: E402
-from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, forcing_batch, logistic_switch_batch, lv_batch,  # noqa: E402
+from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, bessel_ring_batch, forcing_batch, logistic_switch_batch, lv_batch,  # noqa: E402
                             gamma_delay_batch, misc_batch, probit_gate_batch, robertson_batch, seir_batch)
 
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -144,6 +145,17 @@ def gamma_truth():
     d = gamma_delay_batch(16)
     y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
     np.savez(os.path.join(GOLD, "truth_gamma_delay.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
+             tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
+
+
+def bessel_truth():
+    """truth_bessel_ring.npz: 16 draws of ``bessel_ring`` (I1 / I0 of a state, J0 of an inferred wavenumber times t, K0
+    and Y0 of the states; their derivatives through the neighbouring orders; the host functions are scipy.special's
+    jv / yv / iv / kv -- nothing of csrc/sa_math_bessel.h is on this side)."""
+    prob = make("bessel_ring")
+    d = bessel_ring_batch(16)
+    y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
+    np.savez(os.path.join(GOLD, "truth_bessel_ring.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
              tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
 
 
@@ -312,6 +324,9 @@ def main():
     if "--gamma" in sys.argv:
         gamma_truth()
         return
+    if "--bessel" in sys.argv:
+        bessel_truth()
+        return
     # ---------------- DVODE statistics ----------------
     def lv_f(t, y, a, b, c, d):
         return [a * y[0] - b * y[0] * y[1], d * y[0] * y[1] - c * y[1]]
@@ -402,6 +417,7 @@ def main():
     transcendental_truth()
     inverse_erf_truth()
     gamma_truth()
+    bessel_truth()
     sweep_truth()
     print("done")
 

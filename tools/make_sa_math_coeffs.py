@@ -1,14 +1,16 @@
-"""Coefficients of sunode_amd/csrc/sa_math_inv.h (inverse trigonometric / hyperbolic functions, erf, erfc) and of
-sunode_amd/csrc/sa_math_gamma.h (lgamma, tgamma, digamma, trigamma).
+"""Coefficients of sunode_amd/csrc/sa_math_inv.h (inverse trigonometric / hyperbolic functions, erf, erfc), of
+sunode_amd/csrc/sa_math_gamma.h (lgamma, tgamma, digamma, trigamma) and of sunode_amd/csrc/sa_math_bessel.h (J, Y, I, K
+of the orders 0 and 1).
 
 Every polynomial of that header is a Chebyshev-node interpolant (near-minimax) computed here with mpmath at 120
 digits, converted to the monomial basis of the header's own variable, rounded to double and then MEASURED: the
 error of the rounded polynomial against the function, in exact arithmetic, over 1 001 points of the fit
-interval.  Nothing is transcribed from another library.
+interval (201 points for sa_math_bessel.h, whose functions are expensive at that precision).  Nothing is transcribed from another library.
 
     python tools/make_sa_math_coeffs.py            # prints the literal blocks the headers carry
     python tools/make_sa_math_coeffs.py --check    # compares them with the headers' text (exit status 1 on a difference)
-    python tools/make_sa_math_coeffs.py --gamma    # (with either form) only sa_math_gamma.h; --inv: only sa_math_inv.h
+    python tools/make_sa_math_coeffs.py --gamma    # (with either form) only sa_math_gamma.h; --inv: only sa_math_inv.h;
+                                                   # --bessel: only sa_math_bessel.h (its 50 fits run in parallel)
 
 Sets (variable, interval, form):
 
@@ -31,6 +33,20 @@ shift x + 1 of a small one or the reflection 1 - x / -x of a negative one):
             piece 3     D(w) = (ln y - 1/(2y) - psi(y)) / w,  w = 1/y^2 in [0, 1/64]
   TRIGAMMA  pieces 0-2  psi'(y),  y = c_i + w in [1, 2], [2, 4], [4, 8]
             piece 3     T(w) = (y psi'(y) - 1 - 1/(2y)) / w,  w = 1/y^2 in [0, 1/64]
+
+sa_math_bessel.h: one Horner chain per function of order 0 / 1, coefficients selected among the pieces of |x| (the
+orders >= 2 are recurrences and series without fitted coefficients):
+
+  J0, J1    pieces 0-2  J0(x) | J1(x)/x on [0, 1.5];  J(x) / (x - z) on the piece that holds the first zero z (two
+                        words);  J(x) up to 8 (error relative to the modulus M = |H^(1)|), all in x - c
+            pieces 3-4  P(1/x) on [8, 16], [16, inf) in 1/x - c;  J0Q, J1Q: Q(1/x) on the same pieces, where
+                        H^(1)_n(x) = sqrt(2/(pi x)) (P + i Q) exp(i (x - n pi/2 - pi/4))
+  Y0, Y1    pieces 1-4  Y(x) on [0.5, 1.25], [1.25, 2.5], [2.5, 5], [5, 8] in x - c, the first zero factored out of its
+                        piece;  pieces 5-6: P as for J.  Y0S, Y1S: the polynomials A, B of x^2 on [0, 0.25] of
+                        Y0 = ln x A + B, Y1 = x (ln x A + B) - (2/pi)/x
+  I0, I1    piece 0     I0(x) | I1(x)/x in x^2 on [0, 64];  pieces 1-2: sqrt(x) exp(-x) I(x) in 1/x - c on [8, 16], [16, inf)
+  K0, K1    pieces 1-5  sqrt(x) exp(x) K(x) in 1/x - c on [1, 2], [2, 4], [4, 8], [8, 16], [16, inf).  K0S, K1S: the
+                        polynomials A, B of x^2 on [0, 1] of K0 = -ln x A + B, K1 = 1/x + x (ln x A + B)
 """
 from __future__ import annotations
 
@@ -43,6 +59,7 @@ import mpmath as mp
 mp.mp.dps = 120
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sunode_amd", "csrc", "sa_math_inv.h")
 HEADER_GAMMA = os.path.join(os.path.dirname(HEADER), "sa_math_gamma.h")
+HEADER_BESSEL = os.path.join(os.path.dirname(HEADER), "sa_math_bessel.h")
 
 #: interval boundaries of atan's argument reduction (|x|): the header's SAM_ATAN_B1..4; the reduced argument is
 #: largest, 7/16, at the upper end of the first interval
@@ -68,25 +85,35 @@ def lit(x) -> str:
     return repr(float(x))
 
 
-def fit(f, lo, hi, weight=None, target=TARGET, centred=False, nmin=4, nmax=40):
+def fit(f, lo, hi, weight=None, target=TARGET, centred=False, nmin=4, nmax=40, npts=1000, stride=1):
     """Smallest-degree Chebyshev interpolant of f on [lo, hi] (monomial basis in x, or in x - (lo + hi)/2 when
     ``centred``) whose error, BEFORE its coefficients are rounded to double, is below ``target`` relative to
     ``weight(x)`` (default: |f(x)| itself) -- the size of the quantity the header forms from the polynomial.
+    ``npts``: the error is measured at npts + 1 equidistant points.  ``stride`` > 1: the degrees are tried ``stride`` apart
+    first and then downwards one by one from the first that passes (the same degree where the error falls with the
+    degree; fewer evaluations of an expensive f).
     -> (double coefficients low..high, that error measured again AFTER the rounding, centre)."""
     lo, hi = mp.mpf(lo), mp.mpf(hi)
     c = (lo + hi) / 2 if centred else mp.mpf(0)
     g = (lambda w: f(c + w))
     a, b = lo - c, hi - c
-    pts = [a + (b - a) * mp.mpf(k) / 1000 for k in range(1001)]
+    pts = [a + (b - a) * mp.mpf(k) / npts for k in range(npts + 1)]
     want = [g(w) for w in pts]
     scale = [abs(v) if weight is None else abs(weight(c + w)) for v, w in zip(want, pts)]
 
     def worst(poly):
         return max(abs(mp.polyval(poly, w) - v) / sc for w, v, sc in zip(pts, want, scale) if sc != 0)
-    for n in range(nmin, nmax):
+    best = None
+    for n in range(nmin, nmax, stride):
         coeffs = mp.chebyfit(g, [a, b], n)                       # highest power first
         if worst(coeffs) < target:
-            rounded = [mp.mpf(float(v)) for v in coeffs]
+            best = coeffs
+            for m in range(n - 1, max(n - stride, nmin - 1), -1):
+                coeffs = mp.chebyfit(g, [a, b], m)
+                if not worst(coeffs) < target:
+                    break
+                best = coeffs
+            rounded = [mp.mpf(float(v)) for v in best]
             return [float(v) for v in rounded[::-1]], worst(rounded), c
     raise RuntimeError("no fit of degree < %d reaches %s" % (nmax, mp.nstr(target, 3)))
 
@@ -315,6 +342,183 @@ def gamma_blocks():
     return out
 
 
+# ---- sa_math_bessel.h ----
+#: piece boundaries in x (SAM_<FN>_B<k>): the pieces below 8 are fitted in x - c (I: in x^2), those from 8 on (J, Y, I) and
+#: all pieces of K in 1/x - c; below their first boundary Y and K take the logarithmic form
+J0_BOUNDS = ("1.5", "4.0", "8.0", "16.0")
+J1_BOUNDS = ("1.5", "5.0", "8.0", "16.0")
+Y0_BOUNDS = ("0.5", "1.25", "2.5", "5.0", "8.0", "16.0")
+Y1_BOUNDS = ("0.5", "1.25", "2.5", "5.0", "8.0", "16.0")
+I_BOUNDS = ("8.0", "16.0")
+K_BOUNDS = ("1.0", "2.0", "4.0", "8.0", "16.0")
+
+
+def bessel_zero(f, guess):
+    return mp.findroot(f, mp.mpf(guess))
+
+
+def hankel_pq(n, x):
+    chi = x - (mp.mpf(n) / 2 + mp.mpf(1) / 4) * mp.pi
+    v = mp.hankel1(n, x) * mp.expj(-chi) * mp.sqrt(mp.pi * x / 2)
+    return v.real, v.imag
+
+
+def bessel_k(n, x):
+    """K_n(x) at the working precision.  mpmath's besselk takes seconds per value for an integer order and 16 < x < 150 at
+    120 digits; this is the same limit, pi/2 (I_-v - I_v) / sin(pi v) averaged over v = n +- 10^-(dps/2 + 5) (the error
+    is of second order in the offset), with the digits the difference cancels added; beyond 200, where Hankel's
+    asymptotic series reaches the precision, Tricomi's U."""
+    if x > 200:
+        return mp.sqrt(mp.pi) * (2 * x) ** n * mp.exp(-x) * mp.hyperu(n + mp.mpf(1) / 2, 2 * n + 1, 2 * x)
+    dps = mp.mp.dps
+    with mp.workdps(2 * dps + 70 + int(0.9 * float(x))):
+        d = mp.mpf(10) ** -(dps // 2 + 5)
+
+        def kv(v):
+            return mp.pi / 2 * (mp.besseli(-v, x) - mp.besseli(v, x)) / mp.sin(v * mp.pi)
+        r = (kv(n + d) + kv(n - d)) / 2
+    return +r
+
+
+def modulus(n, x):
+    return abs(mp.hankel1(n, x))
+
+
+_JOBS = []
+
+
+def _run_job(k):
+    args, kwargs = _JOBS[k]
+    return fit(*args, **kwargs)
+
+
+def _fit_all():
+    """The fits of ``_JOBS`` (independent of each other) over the processors: forked workers read the closures."""
+    import multiprocessing
+    with multiprocessing.get_context("fork").Pool(min(len(os.sched_getaffinity(0)), 16)) as pool:
+        return pool.map(_run_job, range(len(_JOBS)), chunksize=1)
+
+
+def bessel_blocks():
+    """Pass 1 declares every fit (``later``), the fits run in parallel, pass 2 writes the text."""
+    del _JOBS[:]
+    _bessel_text(None)
+    return _bessel_text(_fit_all())
+
+
+def _bessel_text(results):
+    out = {}
+    count = [0]
+
+    def fit(*args, **kwargs):                                   # (shadows the module's fit inside this function)
+        count[0] += 1
+        kwargs.update(npts=200, stride=4)
+        if results is None:
+            _JOBS.append((args, kwargs))
+            return [0.0] * 4, mp.mpf(1), mp.mpf(0)
+        return results[count[0] - 1]
+    j0z = bessel_zero(lambda v: mp.besselj(0, v), "2.4048")
+    j1z = bessel_zero(lambda v: mp.besselj(1, v), "3.8317")
+    y0z = bessel_zero(lambda v: mp.bessely(0, v), "0.8936")
+    y1z = bessel_zero(lambda v: mp.bessely(1, v), "2.1971")
+    lines = []
+    for name, value in (("BPIO4", mp.pi / 4), ("BE32", mp.exp(32)), ("J0_Z", j0z), ("J1_Z", j1z), ("Y0_Z", y0z), ("Y1_Z", y1z)):
+        hi, lo = hi_lo(value)
+        lines += ["#define SAM_%s_HI %s" % (name, hi), "#define SAM_%s_LO %s" % (name, lo)]
+    # factors that enter one rounded product or quotient: one word
+    for name, value in (("BSQ2OPI", mp.sqrt(2 / mp.pi)), ("B2OPI", 2 / mp.pi), ("BISQ2PI", 1 / mp.sqrt(2 * mp.pi))):
+        lines.append("#define SAM_%s %s" % (name, lit(value)))
+    out["CONST"] = lines
+    tiny = mp.mpf(10) ** -40
+
+    def poly(name, f, hi, text, weight=None):
+        """a plain Horner polynomial in z = x^2 on [0, hi] for the small-argument forms"""
+        c, err, _ = fit(lambda z: f(mp.sqrt(z if z != 0 else tiny)), 0, hi, weight=weight, nmin=3)
+        return (["    /* %s, z = x^2 in [0, %s]: degree %d, error 2^%.1f */" % (text, lit(mp.mpf(hi)), len(c) - 1, float(mp.log(err, 2))),
+                 "#define SAM_%s_POLY(p, z) \\" % name, "    p = %s; \\" % lit(c[-1])]
+                + ["    p = fma(p, z, %s);%s" % (lit(v), " \\" if k else "") for k, v in reversed(list(enumerate(c[:-1])))])
+
+    def direct(f, bounds, tags, weights, first=0):
+        b = [mp.mpf(v) for v in bounds]
+        ps = []
+        for k, (fk, tag, wk) in enumerate(zip(f, tags, weights)):
+            ck, err, cen = fit(fk, b[k], b[k + 1], weight=wk, centred=True, nmin=12, nmax=48)
+            ps.append(("piece %d: %s, x = c + w, c = %s, x in [%s, %s]: degree %d, error 2^%.1f"
+                       % (k + first, tag, lit(cen), lit(b[k]), lit(b[k + 1]), len(ck) - 1, float(mp.log(err, 2))), ck, cen))
+        return ps
+
+    def inverse(f, edges, tag, first, weight=None, limit=None):
+        """pieces in t = 1/x - c; edges ascending in x, the last piece reaches t = 0 (``limit``: the value there)"""
+        ps = []
+        for k in range(len(edges)):
+            thi = 1 / mp.mpf(edges[k])
+            tlo = 1 / mp.mpf(edges[k + 1]) if k + 1 < len(edges) else mp.mpf(0)
+            ck, err, cen = fit(lambda t: limit if t == 0 else f(1 / t), tlo, thi, weight=weight, centred=True, nmin=8, nmax=48)
+            ps.append(("piece %d: %s, 1/x = c + w, c = %s, x in [%s, %s]: degree %d, error 2^%.1f"
+                       % (k + first, tag, lit(cen), lit(mp.mpf(edges[k])), lit(mp.mpf(edges[k + 1])) if k + 1 < len(edges) else "inf",
+                          len(ck) - 1, float(mp.log(err, 2))), ck, cen))
+        return ps
+    one = (lambda v: mp.mpf(1))
+    # ---- J0, J1: direct pieces below 8 (the first zero factored out of its piece), P and Q beyond ----
+    for n, fn, zero, bounds in ((0, "J0", j0z, J0_BOUNDS), (1, "J1", j1z, J1_BOUNDS)):
+        def jf(v, n=n):
+            return mp.besselj(n, v)
+
+        def jzero(v, n=n, zero=zero):
+            return mp.diff(lambda u: mp.besselj(n, u), zero) if abs(v - zero) < mp.mpf(10) ** -60 else mp.besselj(n, v) / (v - zero)
+        first = jf if n == 0 else (lambda v: mp.mpf(1) / 2 if v == 0 else mp.besselj(1, v) / v)
+        ps = direct([first, jzero, jf], ("0.0",) + tuple(bounds[:3]),
+                    ["J0(x)" if n == 0 else "J1(x)/x", "J%d(x)/(x - z), z the first zero" % n, "J%d(x), error relative to M%d" % (n, n)],
+                    [None, None, lambda v, n=n: modulus(n, v)])
+        ps += inverse(lambda v, n=n: hankel_pq(n, v)[0], bounds[2:], "P%d" % n, 3, weight=one, limit=mp.mpf(1))
+        out[fn] = chain(fn, ps)
+        out[fn + "Q"] = chain(fn + "Q", inverse(lambda v, n=n: hankel_pq(n, v)[1], bounds[2:], "Q%d" % n, 0, weight=one, limit=mp.mpf(0)))
+    # ---- Y0, Y1: the logarithmic form below 1/2, direct pieces up to 8, then P and Q of J's chains ----
+    c2 = 2 / mp.pi
+    out["Y0S"] = (poly("Y0A", lambda v: c2 * mp.besselj(0, v), "0.25", "A = (2/pi) J0(x)")
+                  + poly("Y0B", lambda v: mp.bessely(0, v) - c2 * mp.log(v) * mp.besselj(0, v), "0.25", "B = Y0(x) - (2/pi) ln x J0(x)"))
+    out["Y1S"] = (poly("Y1A", lambda v: c2 * mp.besselj(1, v) / v, "0.25", "A = (2/pi) J1(x)/x")
+                  + poly("Y1B", lambda v: (mp.bessely(1, v) + c2 / v - c2 * mp.log(v) * mp.besselj(1, v)) / v, "0.25",
+                         "B = (Y1(x) + (2/pi)/x - (2/pi) ln x J1(x))/x"))
+    for n, fn, zero, bounds, zp in ((0, "Y0", y0z, Y0_BOUNDS, 0), (1, "Y1", y1z, Y1_BOUNDS, 1)):
+        def yf(v, n=n):
+            return mp.bessely(n, v)
+
+        def yzero(v, n=n, zero=zero):
+            return mp.diff(lambda u: mp.bessely(n, u), zero) if abs(v - zero) < mp.mpf(10) ** -60 else mp.bessely(n, v) / (v - zero)
+        mod = (lambda v, n=n: modulus(n, v))
+        fs = [yf] * 4
+        ws = [mod] * 4
+        tags = ["Y%d(x), error relative to M%d" % (n, n)] * 4
+        fs[zp], ws[zp], tags[zp] = yzero, None, "Y%d(x)/(x - z), z the first zero" % n
+        if n == 1:
+            ws[0], tags[0] = None, "Y1(x)"
+        ps = direct(fs, bounds[:5], tags, ws, first=1)
+        ps += inverse(lambda v, n=n: hankel_pq(n, v)[0], bounds[4:], "P%d" % n, 5, weight=one, limit=mp.mpf(1))
+        out[fn] = chain(fn, ps)
+    # ---- I0, I1: the series in z below 8, sqrt(x) exp(-x) I(x) in 1/x beyond ----
+    for n in (0, 1):
+        fn = "I%d" % n
+        small = (lambda v: mp.besseli(0, v)) if n == 0 else (lambda v: mp.besseli(1, v) / v)
+        c, err, _ = fit(lambda z, small=small: small(mp.sqrt(z if z != 0 else tiny)), 0, 64, nmin=12, nmax=48)
+        ps = [("piece 0: %s, w = x^2 in [0, 64.0]: degree %d, error 2^%.1f"
+               % ("I0(x)" if n == 0 else "I1(x)/x", len(c) - 1, float(mp.log(err, 2))), c, None)]
+        ps += inverse(lambda v, n=n: mp.sqrt(v) * mp.exp(-v) * mp.besseli(n, v), I_BOUNDS, "sqrt(x) exp(-x) I%d(x)" % n, 1,
+                      limit=1 / mp.sqrt(2 * mp.pi))
+        out[fn] = chain(fn, ps)
+    # ---- K0, K1: the logarithmic form below 1, sqrt(x) exp(x) K(x) in 1/x beyond ----
+    out["K0S"] = (poly("K0A", lambda v: mp.besseli(0, v), "1.0", "A = I0(x)")
+                  + poly("K0B", lambda v: bessel_k(0, v) + mp.log(v) * mp.besseli(0, v), "1.0", "B = K0(x) + ln x I0(x)"))
+    out["K1S"] = (poly("K1A", lambda v: mp.besseli(1, v) / v, "1.0", "A = I1(x)/x")
+                  + poly("K1B", lambda v: (bessel_k(1, v) - 1 / v - mp.log(v) * mp.besseli(1, v)) / v, "1.0",
+                         "B = (K1(x) - 1/x - ln x I1(x))/x"))
+    for n in (0, 1):
+        fn = "K%d" % n
+        out[fn] = chain(fn, inverse(lambda v, n=n: mp.sqrt(v) * mp.exp(v) * bessel_k(n, v), K_BOUNDS,
+                                    "sqrt(x) exp(x) K%d(x)" % n, 1, limit=mp.sqrt(mp.pi / 2)))
+    return out
+
+
 def check(header, text, want):
     with open(header) as fh:
         hdr = fh.read()
@@ -325,7 +529,7 @@ def check(header, text, want):
             print("%s of %s is not %s" % (macro, header, value))
             bad = 1
     for name, lines in text.items():
-        m = re.search(r"/\* BEGIN GENERATED %s[^\n]*\n(.*?)\n[^\n]*END GENERATED %s" % (name, name), hdr, re.S)
+        m = re.search(r"/\* BEGIN GENERATED %s\b[^\n]*\n(.*?)\n[^\n]*END GENERATED %s\b" % (name, name), hdr, re.S)
         if m is None or m.group(1).strip() != "\n".join(lines).strip():
             print("block %s of %s differs from the generator's output" % (name, header))
             bad = 1
@@ -333,16 +537,22 @@ def check(header, text, want):
 
 
 def main():
-    which = [w for w in ("inv", "gamma") if "--" + w in sys.argv] or ["inv", "gamma"]
+    which = [w for w in ("inv", "gamma", "bessel") if "--" + w in sys.argv] or ["inv", "gamma", "bessel"]
     bad = 0
     for w in which:
-        text = blocks() if w == "inv" else gamma_blocks()
+        text = blocks() if w == "inv" else (gamma_blocks() if w == "gamma" else bessel_blocks())
         if "--check" in sys.argv:
             if w == "inv":
                 want = {"SAM_ATAN_B%d" % (k + 1): v for k, v in enumerate(ATAN_BOUNDS)}
                 want.update({"SAM_ERF_B%d" % (k + 1): v for k, v in enumerate(ERF_BOUNDS)})
                 want.update({"SAM_ERFC_B1": ERFC_DIRECT, "SAM_ERFC_CLAMP": ERFC_CLAMP})
                 bad |= check(HEADER, text, want)
+            elif w == "bessel":
+                want = {"SAM_%s_B%d" % (fn, k + 1): v
+                        for fn, bs in (("J0", J0_BOUNDS), ("J1", J1_BOUNDS), ("Y0", Y0_BOUNDS), ("Y1", Y1_BOUNDS),
+                                       ("I0", I_BOUNDS), ("I1", I_BOUNDS), ("K0", K_BOUNDS), ("K1", K_BOUNDS))
+                        for k, v in enumerate(bs)}
+                bad |= check(HEADER_BESSEL, text, want)
             else:
                 want = {"SAM_%s_B%d" % (fn, k + 1): v for fn, bs in (("LGAMMA", LGAMMA_BOUNDS), ("DIGAMMA", DIGAMMA_BOUNDS),
                                                                       ("TRIGAMMA", TRIGAMMA_BOUNDS)) for k, v in enumerate(bs)}

@@ -198,6 +198,36 @@ def gamma_delay(t, y, p):
     }
 
 
+def mathfn_f(t, y, p):
+    """One or two functions of csrc/sa_math_bessel.h per output -- besselj / bessely / besseli / besselk of integer
+    order -- with a product or a quotient of a state and a differentiated parameter as the argument.  All four families
+    appear; the orders 2 (I, J) and 1 (Y, K) appear directly; the derivatives (sympy: B'_n in terms of B_(n-1) and
+    B_(n+1), -+B_1 for n = 0) bring J1, Y0 and Y2, I1 and I3, K1, J1 and J3, K0 and K2 into the Jacobian, the adjoint
+    and the quadrature: the orders 3 are reachable ONLY through a derivative."""
+    import sympy as sym
+    x, a = y.x, p.a
+    return {"x": [sym.besselj(0, a[0] * x[0]), sym.bessely(1, x[1] / a[1]), sym.besseli(2, a[2] * x[2]),
+                  sym.besselk(0, a[3] * x[3]) + sym.besselj(2, x[3] / a[3]), sym.besselk(1, x[4] / a[4])]}
+
+
+def bessel_ring(t, y, p):
+    """A PyMC-shaped model on the Bessel functions: the order parameter x of a ring of oscillators relaxes towards the
+    von Mises mean resultant length I1(b x) / I0(b x) (coupling b inferred) under a radially symmetric forcing
+    e J0(w t) whose wavenumber w is inferred; the response z follows g x against a linear loss and a screened
+    (Yukawa-type) source q K0(kappa + z^2), whose argument is strictly positive, and is pushed by -r Y1(1 + x - z); the
+    read-out c accumulates Y0(1 + x - z) / 5.  s = 1 + x - z stays above 1/2 for the default draws, where r Y1(s) is
+    small; raising g alone lets z approach 1 + x, and -r Y1(s) ~ 2 r / (pi s) then drives s through zero in finite time
+    with an unbounded slope (a per-instance solver failure; Y is NaN on the negative axis).  Jacobian, adjoint and
+    quadrature carry I2, J1, K1, Y0, Y1 and Y2."""
+    import sympy as sym
+    x, z, c = y.x, y.z, y.c
+    return {
+        "x": p.A * sym.besseli(1, p.b * x) / sym.besseli(0, p.b * x) - p.m * x + p.e * sym.besselj(0, p.w * t),
+        "z": p.g * x - p.d * z + p.q * sym.besselk(0, p.kappa + z * z) - p.r * sym.bessely(1, 1 + x - z),
+        "c": sym.bessely(0, 1 + x - z) / 5 - c / 5,
+    }
+
+
 def huge_pivots(t, y, p):
     """Decay rates of 1e200 on components that are exactly zero: the Newton matrix I - gamma*J has diagonal entries
     around 1e200 (beyond 2^500) while the steps stay of order 1 -- the pivots' reciprocals leave the range in which the
@@ -320,6 +350,13 @@ EXTRA_PROBLEMS = {
         states={"x": (), "z": (), "c": ()},
         rhs=gamma_delay,
         derivative_params=[("k",), ("theta",), ("b",), ("g",), ("A",)],
+    ),
+    "mathfn_f": dict(params={"a": (5,)}, states={"x": (5,)}, rhs=mathfn_f, derivative_params=[("a",)]),
+    "bessel_ring": dict(
+        params={"b": (), "w": (), "g": (), "A": (), "kappa": (), "m": (), "e": (), "d": (), "q": (), "r": ()},
+        states={"x": (), "z": (), "c": ()},
+        rhs=bessel_ring,
+        derivative_params=[("b",), ("w",), ("g",), ("A",), ("kappa",)],
     ),
     "sir2": dict(
         params={"beta": (2,), "C": (2, 2), "gamma": (), "pop": (2,)},
@@ -503,6 +540,19 @@ def gamma_delay_batch(B: int, seed: int = SEED, idx=None):
     y0 = np.concatenate([np.array([0.1, 0.2]) * np.exp(0.1 * zy), np.zeros((len(z), 1))], axis=1)
     tvals = np.linspace(0, 8, 9)
     return dict(ps=ps, pr=np.array([0.5, 0.6, 0.05, 0.4]), y0=y0, tvals=tvals, t0=0.0,
+                grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
+
+
+def bessel_ring_batch(B: int, seed: int = SEED, idx=None):
+    """Draws for ``bessel_ring``: subset (b, w, g, A, kappa), remainder (m, e, d, q, r).  Over t in [0, 8] the argument
+    w t of the forcing runs from 0 to about 12: through the piece boundaries 1.5, 4 and 8 of J0 and its zeros 2.40,
+    5.52, 8.65."""
+    z = np.stack([std_normal(seed, 1320 + k, B, idx) for k in range(5)], axis=1)
+    ps = np.array([2.0, 1.5, 0.3, 1.0, 0.5]) * np.exp(0.1 * z)
+    zy = np.stack([std_normal(seed, 1330 + s, B, idx) for s in range(2)], axis=1)
+    y0 = np.concatenate([np.array([0.1, 0.2]) * np.exp(0.1 * zy), np.zeros((len(z), 1))], axis=1)
+    tvals = np.linspace(0, 8, 9)
+    return dict(ps=ps, pr=np.array([0.5, 0.3, 0.6, 0.2, 0.05]), y0=y0, tvals=tvals, t0=0.0,
                 grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
 
 

@@ -5,7 +5,7 @@
 
 ``mathfn_a`` (exp / log / log1p / expm1 / pow) is the yardstick the inverse / erf problems ``mathfn_c`` (asin / acos /
 atan / atan2), ``mathfn_d`` (asinh / acosh / atanh / erf / erfc) and the gamma-family problem ``mathfn_e`` (loggamma /
-gamma / digamma / trigamma) are compared with: five outputs of one or two
+gamma / digamma / trigamma) and the Bessel problem ``mathfn_f`` (J / Y / I / K of integer order) are compared with: five outputs of one or two
 function calls each, plus their derivatives in the four other callbacks.  Arguments are drawn inside the domains (the
 main paths are branch-free: their cost does not depend on the interval).  Prints the host-side wall time per call (it
 includes the copies of 26 N doubles each way; the kernel time is the profiler's) and the registers / spill slots /
@@ -46,6 +46,8 @@ def main():
             y[:, 3:] = rng.uniform(0.05, 20.0, (N, 2))         # erf / erfc: all pieces
         if name == "mathfn_e":
             y = rng.uniform(0.05, 20.0, (N, 5))                 # all pieces of the positive axis (no reflection)
+        if name == "mathfn_f":
+            y = rng.uniform(0.05, 40.0, (N, 5))                 # every piece of J, Y, I, K up to 40 (I_2: the downward recurrence)
     lam, t = rng.randn(N, 5), rng.uniform(0, 50, N)
     eng = Solver(prob)._engine()
     for k in range(repeats + 1):                               # (the first call loads the code object)
