@@ -36,6 +36,14 @@ the same rule; a non-integer, symbolic or larger order raises.  Functions outsid
 the four lists (``LIBM_ONLY``: cbrt, hypot, exp2, log2, log10) still compile, through
 libm / ocml, without the bit-equality guarantee; ``SympyProblem`` warns about them.
 
+Non-smooth forms: ``Abs / floor / Mod`` are printed by the inherited C99 printer as ``fabs / floor / fmod`` -- exact
+operations, the same bits on every implementation --, ``Piecewise`` and relations as nested ``?:`` selects,
+``Heaviside`` (1/2 at 0) and ``sign`` as compares.  ``Max / Min`` are NOT left to ``fmax / fmin``, whose answer at a
++-0 tie is the implementation's: they are calls of ``sa_max / sa_min`` (``MINMAX_C``, embedded when used).  ``DiracDelta``
+-- the derivative sympy gives ``Heaviside`` and ``sign`` -- is printed as 0.0 (``SympyProblem`` warns: the jump term of
+the sensitivities is not carried).  Number symbols (``pi, E, EulerGamma, Catalan, GoldenRatio, TribonacciConstant``)
+are literals; no ``M_*`` macro of <math.h> is ever printed.
+
 Callback ABI (all arrays are flat ``double``):
 
     int sa_rhs     (double t, const double* y, const double* ps, const double* pr, double* out /*n*/);
@@ -204,12 +212,39 @@ HELPERS_C = r"""
 """
 
 
+#: Max / Min of a generated right-hand side: compare-and-select with ONE written-down rule where C leaves fmax / fmin to
+#: the implementation (the device's v_max_f64 and a host's fmax / maxsd answer the +-0 tie differently: measured,
+#: tests/test_gpu_nonsmooth.py).  The rule is IEEE 754-2019 maximumNumber / minimumNumber: a NaN operand is ignored (the
+#: result is NaN only if both are), and -0 < +0: sa_max(+0, -0) = +0, sa_min(+0, -0) = -0 in either order -- the sum of
+#: two zeros is -0 only if both are, so a + b decides the tie of the maximum and -(-a - b) that of the minimum.  Embedded
+#: only into the headers that call them: every other header keeps its text.
+MINMAX_C = r"""
+/* Max / Min: IEEE 754-2019 maximumNumber / minimumNumber (NaN operand ignored, -0 < +0); codegen.MINMAX_C */
+SA_FN double sa_max(double a, double b)
+{
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return (a == 0.0) ? a + b : a;
+    return (a > b) ? a : b;
+}
+SA_FN double sa_min(double a, double b)
+{
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return (a == 0.0) ? -(-a - b) : a;
+    return (a < b) ? a : b;
+}
+"""
+
+
 class HipExprPrinter(C99CodePrinter):
     """C99 printer with symbol -> array-slot mapping and product-expanded powers."""
 
     def __init__(self, symbol_map: Dict[str, str]):
         super().__init__({"allow_unknown_functions": False})
         self._symbol_map = symbol_map
+        # no M_PI / M_E / M_SQRT2 ... of <math.h>: they are not part of C99, every constant is printed as a literal
+        self.math_macros = {}
 
     def _print_Symbol(self, expr):
         name = expr.name
@@ -270,6 +305,14 @@ class HipExprPrinter(C99CodePrinter):
 
     def _print_Pi(self, expr):
         return "3.141592653589793"          # (a literal: M_PI is not part of C99)
+
+    def _print_NumberSymbol(self, expr):
+        """E, EulerGamma, Catalan, GoldenRatio, TribonacciConstant: the correctly rounded double as a literal, like pi
+        (the inherited printer asks for a ``const double`` declaration in front of the statement instead, which the
+        one-statement-per-output form of the callbacks has no place for)."""
+        return repr(float(expr.evalf(30)))
+
+    _print_Exp1 = _print_EulerGamma = _print_Catalan = _print_GoldenRatio = _print_TribonacciConstant = _print_NumberSymbol
 
     def _print_Rational(self, expr):
         return "(%d.0/%d.0)" % (expr.p, expr.q)
@@ -431,6 +474,25 @@ class HipExprPrinter(C99CodePrinter):
     def _print_sign(self, expr):
         x = self._print(expr.args[0])
         return "(((%s) > 0.0) - ((%s) < 0.0))" % (x, x)
+
+    # Max / Min: sa_max / sa_min (MINMAX_C), nested in sympy's canonical argument order like the inherited fmax / fmin
+    def _nested_call(self, name, args):
+        if len(args) == 1:
+            return self._print(args[0])
+        return "%s(%s, %s)" % (name, self._print(args[0]), self._nested_call(name, args[1:]))
+
+    def _print_Max(self, expr):
+        from sympy.core.sorting import default_sort_key
+        return self._nested_call("sa_max", sorted(expr.args, key=default_sort_key))
+
+    def _print_Min(self, expr):
+        from sympy.core.sorting import default_sort_key
+        return self._nested_call("sa_min", sorted(expr.args, key=default_sort_key))
+
+    def _print_DiracDelta(self, expr):
+        # the derivative of Heaviside / sign almost everywhere -- what sympy itself derives for the same switch written
+        # as a Piecewise.  The jump term of the sensitivities is NOT carried (SympyProblem warns: delta_functions)
+        return "0.0"
 
 
 #: callbacks with more output statements than this are emitted as a chain of chunk functions
@@ -1084,6 +1146,8 @@ def generate_problem_source(
         parts[6] += "\n" + math_gamma_c()
     if uses_bessel:             # the fourth block builds on the first only (sa_exp, sa_log, the kernels of sa_sin)
         parts[6] += "\n" + math_bessel_c()
+    if any(_MINMAX_CALL.search(part) for part in parts[7:] if part):
+        parts[6] += "\n" + MINMAX_C
     return "\n".join(parts)
 
 
@@ -1096,6 +1160,8 @@ _MATH_INV_CALL = re.compile(r"\bsa_(asin|acos|atan|atan2|asinh|acosh|atanh|erf|e
 _MATH_GAMMA_CALL = re.compile(r"\bsa_(lgamma|tgamma|digamma|trigamma)\(")
 #: ... and of csrc/sa_math_bessel.h
 _MATH_BESSEL_CALL = re.compile(r"\bsa_bessel_(j|y|i|k)\(")
+#: ... and of MINMAX_C
+_MINMAX_CALL = re.compile(r"\bsa_(max|min)\(")
 #: functions the C99 printer would hand to libm / ocml (not bit-reproducible between host and device)
 LIBM_ONLY = ("cbrt", "exp2", "log2", "log10", "hypot")
 
@@ -1181,6 +1247,25 @@ def libm_calls(source: str) -> List[str]:
     """Names of libm-only functions a generated header calls: such a model integrates, but the device (ocml) and
     the host (libm) may round them differently -- bit-equality with the oracle is then not guaranteed."""
     return sorted({m for m in LIBM_ONLY if re.search(r"(?<![\w.])%s\(" % m, source)})
+
+
+def delta_functions(rhs, derivatives) -> List[str]:
+    """The ``Heaviside`` / ``sign`` terms of a right-hand side (``rhs``: its expressions) whose derivative with respect to
+    a state or a differentiated parameter is a ``DiracDelta`` in ``derivatives`` (the Jacobian and df/dp): the generated
+    code evaluates that delta as 0 -- the derivative almost everywhere --, so sensitivities and adjoint gradients of
+    such a model lack the jump term of the switching surface.  ``Heaviside(t - 1)`` has no such derivative."""
+    deltas = set()
+    for e in derivatives:
+        deltas |= sym.sympify(e).atoms(sym.DiracDelta)
+    if not deltas:
+        return []
+    args = {d.args[0] for d in deltas}
+    found = set()
+    for e in rhs:
+        for f in sym.sympify(e).atoms(sym.Heaviside, sym.sign):
+            if f.args[0] in args:
+                found.add(str(f))
+    return sorted(found) or sorted(str(d) for d in deltas)
 
 
 def source_hash(text: str, extra: Iterable[str] = ()) -> str:

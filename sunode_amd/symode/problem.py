@@ -659,6 +659,13 @@ class SympyProblem:
                 warnings.warn("the generated callbacks call %s through libm (host) / ocml (device): the device's results "
                               "are not guaranteed to equal a host run's bit for bit for this model"
                               % ", ".join(libm), UserWarning, stacklevel=2)
+            jumps = codegen.delta_functions(self._sym_dydt, list(np.asarray(self._sym_dydt_jac, dtype=object).ravel())
+                                            + list(np.asarray(self._sym_dydp, dtype=object).ravel()))
+            if jumps:
+                import warnings
+                warnings.warn("the right-hand side jumps on a state- or parameter-dependent surface (%s): the generated "
+                              "derivative treats DiracDelta as 0, so adjoint and forward-sensitivity gradients omit the "
+                              "jump term of that surface" % ", ".join(jumps), UserWarning, stacklevel=2)
         return self._native_source
 
     # ------------------------------------------------------------------

@@ -18,6 +18,7 @@ Usage: python tools/make_golden_truth.py   (a few minutes; outputs are committed
        python tools/make_golden_truth.py --inverse-erf    (only truth_probit_gate.npz: see ``inverse_erf_truth``)
        python tools/make_golden_truth.py --gamma    (only truth_gamma_delay.npz: see ``gamma_truth``)
        python tools/make_golden_truth.py --bessel    (only truth_bessel_ring.npz: see ``bessel_truth``)
+       python tools/make_golden_truth.py --nonsmooth    (only truth_kinked.npz, truth_threshold_sir8.npz: see ``nonsmooth_truth``)
 """
 from __future__ import annotations
 
@@ -35,7 +36,8 @@ sys.path.insert(0, ROOT)
 from sunode_amd import SympyProblem  # noqa: E402
 from sunode_amd.symode.problem import HOST_FUNCTIONS  # noqa: E402
 from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, bessel_ring_batch, forcing_batch, logistic_switch_batch, lv_batch,  # noqa: E402
-                            gamma_delay_batch, misc_batch, probit_gate_batch, robertson_batch, seir_batch)
+                            gamma_delay_batch, kinked_batch, misc_batch, probit_gate_batch, robertson_batch, seir_batch,
+                            threshold_sir_batch)
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -70,13 +72,16 @@ def augmented_rhs(prob):
     return rhs
 
 
-def truth_batch(prob, y0, ps, pr, t0, tvals, grads, method, rtol=1e-13, atol=1e-15):
+def truth_batch(prob, y0, ps, pr, t0, tvals, grads, method, rtol=1e-13, atol=1e-15, return_sens=False):
+    """-> y_out [B, n_t, n], dL/dp [B, p], dL/dy0 [B, n] (and, ``return_sens``, the forward sensitivities
+    [B, n_t, p, n] they were contracted from)."""
     n, p = prob.n_states, prob.n_params
     B = y0.shape[0]
     rhs = augmented_rhs(prob)
     y_out = np.zeros((B, len(tvals), n))
     grad_p = np.zeros((B, p))
     grad_y0 = np.zeros((B, n))
+    sens = np.zeros((B, len(tvals), p, n))
     for b in range(B):
         prb = pr if pr.ndim == 1 else pr[b]
         z0 = np.concatenate([y0[b], np.zeros(n * p), np.eye(n).ravel()])
@@ -90,7 +95,10 @@ def truth_batch(prob, y0, ps, pr, t0, tvals, grads, method, rtol=1e-13, atol=1e-
         S0 = z[:, n + n * p:].reshape(len(tvals), n, n)        # [k, j(y0 index), i(state)]
         grad_p[b] = np.einsum("ki,kpi->p", g, S)
         grad_y0[b] = np.einsum("ki,kji->j", g, S0)
+        sens[b] = S
         print("  truth instance", b, "nfev", sol.nfev, flush=True)
+    if return_sens:
+        return y_out, grad_p, grad_y0, sens
     return y_out, grad_p, grad_y0
 
 
@@ -157,6 +165,50 @@ def bessel_truth():
     y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
     np.savez(os.path.join(GOLD, "truth_bessel_ring.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
              tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
+
+
+#: what the two DOP853 runs of ``nonsmooth_truth`` (rtol 1e-13 and 1e-11) must agree to, in the tests' own error
+#: measures: a hundredth of the bars of tests/test_nonsmooth.py (TRUTH_BARS there; the test re-checks the stored figures)
+NONSMOOTH_AGREE = {"kinked": dict(y=6.9e-9, grad_params=9.1e-9, grad_y0=8.6e-9, sens=4.3e-8),
+                   "threshold_sir8": dict(y=1.3e-8, grad_params=3.1e-8, grad_y0=4.6e-8)}
+
+
+def truth_errors(got, ref):
+    """{quantity: error of ``got`` against ``ref``} in the measures of the truth tests: states relative to the largest
+    value of the component over the batch, gradients relative to the largest component of the draw's gradient,
+    sensitivities relative to the largest value of the (parameter, state) pair over the batch."""
+    out = {"y": float(np.max(np.abs(got["y_out"] - ref["y_out"]) / np.abs(ref["y_out"]).max(axis=(0, 1))))}
+    for key, short in (("grad_params", "grad_params"), ("grad_y0", "grad_y0")):
+        out[short] = float(np.max(np.abs(got[key] - ref[key]) / np.abs(ref[key]).max(axis=1, keepdims=True)))
+    if "sens" in got and "sens" in ref:
+        scale = np.abs(ref["sens"]).max(axis=(0, 1))
+        out["sens"] = float(np.max(np.abs(got["sens"] - ref["sens"]) / np.where(scale > 0, scale, 1.0)))
+    return out
+
+
+def nonsmooth_truth():
+    """truth_kinked.npz, truth_threshold_sir8.npz: 8 draws each of the models with a continuous but kinked right-hand
+    side (Max / Abs / Piecewise of a state; numpy's amax / abs / select / heaviside / sign on this side).  A one-step
+    method's error estimate across a kink is not a given, so every fixture is integrated twice -- DOP853 at rtol 1e-13
+    (stored) and at 1e-11 -- and the two must agree to ``NONSMOOTH_AGREE``, a hundredth of the bars the tests apply; the
+    measured agreement is stored next to the truth (``agree_<quantity>``).  ``kinked`` also stores the forward
+    sensitivities dy/dp [B, n_t, p, n]."""
+    for name, batch in (("kinked", kinked_batch), ("threshold_sir8", lambda B: threshold_sir_batch(B, 8))):
+        prob = make(name)
+        d = batch(8)
+        runs = []
+        for rtol, atol in ((1e-13, 1e-15), (1e-11, 1e-13)):
+            y_out, gp, gy0, sens = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853",
+                                               rtol=rtol, atol=atol, return_sens=True)
+            runs.append(dict(y_out=y_out, grad_params=gp, grad_y0=gy0, sens=sens))
+        agree = truth_errors(runs[1], runs[0])
+        print(name, "DOP853 1e-11 against 1e-13:", agree, flush=True)
+        for key, bound in NONSMOOTH_AGREE[name].items():
+            assert agree[key] <= bound, (name, key, agree[key], bound)
+        extra = {"sens": runs[0]["sens"]} if name == "kinked" else {}
+        np.savez(os.path.join(GOLD, "truth_%s.npz" % name), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
+                 tvals=d["tvals"], grads=d["grads"], y_out=runs[0]["y_out"], grad_params=runs[0]["grad_params"],
+                 grad_y0=runs[0]["grad_y0"], **extra, **{"agree_" + k: v for k, v in agree.items()})
 
 
 def sweep_truth():
@@ -327,6 +379,9 @@ def main():
     if "--bessel" in sys.argv:
         bessel_truth()
         return
+    if "--nonsmooth" in sys.argv:
+        nonsmooth_truth()
+        return
     # ---------------- DVODE statistics ----------------
     def lv_f(t, y, a, b, c, d):
         return [a * y[0] - b * y[0] * y[1], d * y[0] * y[1] - c * y[1]]
@@ -418,6 +473,7 @@ def main():
     inverse_erf_truth()
     gamma_truth()
     bessel_truth()
+    nonsmooth_truth()
     sweep_truth()
     print("done")
 

@@ -328,8 +328,82 @@ def sir_two_groups(t, y, p):
             "I": [force[i] * y.S[i] - p.gamma * y.I[i] for i in range(2)]}
 
 
+def nonsmooth_fn(t, y, p):
+    """A catalogue of the non-smooth forms a right-hand side may contain -- Abs, Max / Min (two and three arguments,
+    nested), Max(0, .)**2, Piecewise (with and without a default branch, And, Ne), floor, Mod, Heaviside and sign of the
+    time and of a state -- next to the power and constant forms of the inherited printer (x**9, x**-9, x**a, log(x, 10);
+    E, EulerGamma, Catalan, GoldenRatio), each multiplied into a state so that Jacobian, adjoint and quadrature carry
+    it.  Output 1 is EXACTLY Min(Max(a1 (x0 - a0), 0), x1): compare / select on one product, so that the sign of a zero
+    result (a1 < 0 at x0 == a0: the product is -0) reaches an output."""
+    import sympy as sym
+    x, a = y.x, p.a
+    half3 = sym.Rational(3, 2)
+    return {"x": [
+        x[0] * sym.Abs(x[0] - a[0]) + x[1] * sym.Max(x[1], a[1] * x[2]) + x[2] * sym.Min(x[0], x[3], a[3]),
+        sym.Min(sym.Max(a[1] * (x[0] - a[0]), 0), x[1]),
+        (x[2] * sym.Min(sym.Max(x[0], a[2]), sym.Max(x[1], a[0] * x[3]), 2) + sym.Max(0, x[2] - a[2]) ** 2
+         + x[4] * sym.Max(x[2], x[3], a[4])),
+        (x[3] * sym.Piecewise((a[3] * x[3], x[3] < a[3]), (a[3] ** 2, True))
+         + x[0] * sym.Piecewise((x[0] - a[0], x[0] < a[0]), (2 * (x[0] - a[0]), x[0] >= a[0]))
+         + x[1] * sym.Piecewise((a[1], sym.And(t > 1, t < 2)), (0, True))
+         + x[2] * sym.Piecewise((a[2], sym.Ne(x[2], a[0])), (1, True))
+         + x[3] * (sym.floor(t) + sym.Mod(t, 2) + sym.Heaviside(t - 1) + sym.sign(t - half3))),
+        (sym.Heaviside(x[0] - a[0]) * x[1] + x[4] * sym.sign(x[1] - a[0]) + sym.Catalan * a[4] * x[4] ** 9
+         + sym.GoldenRatio * x[4] ** -9 + sym.EulerGamma * x[3] ** a[3] + sym.E * x[4] * sym.log(x[4], 10)),
+    ]}
+
+
+#: the literal switching level of ``kinked``'s third state
+KINKED_Q = 0.25
+
+
+def kinked(t, y, p):
+    """A continuous right-hand side with three kinks, each on a surface the solution crosses: the activity x decays
+    through the level c (Abs(x - c) damps y), the resource y rises through the threshold th (Max(y - th, 0) feeds x) and
+    the read-out z rises through the literal level 1/4, where its loss rate doubles (a continuous Piecewise).  The
+    Jacobian jumps on every surface (Heaviside / sign of a state); the right-hand side does not, so sensitivities and
+    adjoint gradients have no jump term."""
+    import sympy as sym
+    x, yy, z = y.x, y.y, y.z
+    q = sym.Rational(1, 4)
+    return {
+        "x": -p.k * x + sym.Max(yy - p.th, 0),
+        "y": p.r * (1 - yy) - sym.Abs(x - p.c) / 5,
+        "z": yy - sym.Piecewise((z, z < q), (q + 2 * (z - q), True)),
+    }
+
+
+def make_threshold_sir(M):
+    """M groups x (S, I) with a THRESHOLD force of infection -- group j infects only with what it has above th:
+    sum_j C[i, j] Max(I[j] - th, 0) -- and a recovery rate that saturates above I = 1 (a continuous Piecewise).  Written
+    as loops over the groups: a lane family at M = 4 and 8 (one group per lane: lanes of one instance sit on different
+    branches of Max and of the Piecewise), SA_SUM terms (one term per lane) at M = 16."""
+    def threshold_sir(t, y, p):
+        import sympy as sym
+        force = [p.beta[i] * sum(p.C[i, j] * sym.Max(y.I[j] - p.th, 0) for j in range(M)) for i in range(M)]
+        rec = [p.g * sym.Abs(y.I[i]) * sym.Piecewise((1, y.I[i] < 1), (2 - 1 / y.I[i], True)) for i in range(M)]
+        return {"S": [-force[i] * y.S[i] for i in range(M)],
+                "I": [force[i] * y.S[i] - rec[i] for i in range(M)]}
+    return threshold_sir
+
+
+def threshold_sir(M):
+    return dict(params={"beta": (M,), "g": (), "th": (), "C": (M, M)}, states={"S": (M,), "I": (M,)},
+                rhs=make_threshold_sir(M), derivative_params=[("beta",), ("g",), ("th",)])
+
+
 #: test-only problems without reference-generated golden fixtures
 EXTRA_PROBLEMS = {
+    "nonsmooth_fn": dict(params={"a": (5,)}, states={"x": (5,)}, rhs=nonsmooth_fn, derivative_params=[("a",)]),
+    "kinked": dict(
+        params={"th": (), "c": (), "k": (), "r": ()},
+        states={"x": (), "y": (), "z": ()},
+        rhs=kinked,
+        derivative_params=[("th",), ("c",), ("k",), ("r",)],
+    ),
+    "threshold_sir4": threshold_sir(4),
+    "threshold_sir8": threshold_sir(8),
+    "threshold_sir16": threshold_sir(16),
     "logistic_switch": dict(
         params={"log_r": (), "log_K": (), "k": (), "x_half": (), "q": (), "m": ()},
         states={"x": (), "v": ()},
@@ -554,6 +628,41 @@ def bessel_ring_batch(B: int, seed: int = SEED, idx=None):
     tvals = np.linspace(0, 8, 9)
     return dict(ps=ps, pr=np.array([0.5, 0.3, 0.6, 0.2, 0.05]), y0=y0, tvals=tvals, t0=0.0,
                 grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
+
+
+def kinked_batch(B: int, seed: int = SEED, idx=None):
+    """Draws for ``kinked``: subset (th, c, k, r), no remainder.  th, c, k, r = (0.5, 0.45, 1.2, 0.8) exp(0.25 z) and
+    y0 = (1, 0.1, 0) (x, y scaled by exp(0.1 z')): x falls through c around t = 0.7, y rises through th around 0.9 and z
+    through 1/4 around 1.3, each with a spread of several tenths between draws -- many steps at rtol 1e-8.  Every fifth
+    draw (global index 4 mod 5) has th raised beyond 1, the bound of y: it stays below its threshold for good."""
+    z = np.stack([std_normal(seed, 1340 + k, B, idx) for k in range(4)], axis=1)
+    ps = np.array([0.5, 0.45, 1.2, 0.8]) * np.exp(0.25 * z)
+    index = np.arange(B) if idx is None else np.asarray(idx)
+    ps[index % 5 == 4, 0] += 1.0
+    zy = np.stack([std_normal(seed, 1350 + s, B, idx) for s in range(2)], axis=1)
+    y0 = np.concatenate([np.array([1.0, 0.1]) * np.exp(0.1 * zy), np.zeros((len(z), 1))], axis=1)
+    tvals = np.linspace(0, 5, 11)
+    return dict(ps=ps, pr=np.zeros(0), y0=y0, tvals=tvals, t0=0.0,
+                grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
+
+
+def threshold_sir_batch(B: int, M: int, seed: int = SEED, idx=None):
+    """Draws for ``threshold_sir(M)``: subset (beta[M], g, th), remainder C (M x M, shared).  The infected start between
+    0.3 and 3 (log-spaced over the groups, jittered per draw) around the threshold th = exp(0.3 z): in every instance
+    some groups are above th and some below at the same time, and above and below the saturation level I = 1."""
+    stream = 1360 + 40 * M
+    C = (0.2 + np.abs(std_normal(seed, stream, M * M)).reshape(M, M)) / M + 0.5 * np.eye(M)
+    z = np.stack([std_normal(seed, stream + 1 + k, B, idx) for k in range(M + 2)], axis=1)
+    base = np.concatenate([0.08 + 0.01 * (np.arange(M) % 5), [0.3, 1.0]])
+    ps = base * np.exp(0.2 * z)
+    ps[:, -1] = np.exp(0.3 * z[:, -1])
+    zi = np.stack([std_normal(seed, stream + 20 + (i % 16), B, idx) for i in range(M)], axis=1)
+    I0 = 0.3 * 10.0 ** (np.arange(M) / max(M - 1, 1)) * np.exp(0.1 * zi)
+    S0 = np.full_like(I0, 10.0) + np.arange(M) % 3
+    y0 = np.concatenate([S0, I0], axis=1)
+    tvals = np.linspace(0, 6, 7)
+    return dict(ps=ps, pr=C.ravel(), y0=y0, tvals=tvals, t0=0.0,
+                grads=_cotangents(len(z), len(tvals), 2 * M, idx), rtol=1e-8, atol=1e-8)
 
 
 def misc_batch(B: int, seed: int = SEED, idx=None):
