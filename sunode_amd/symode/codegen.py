@@ -15,26 +15,22 @@ as host functions (test oracle / CPU baseline).  Kept from the reference:
   (``symode/problem.py:266-269``).
 
 Different from the reference on purpose: integer powers are expanded to
-products, no ``fastmath`` style re-association is allowed, and ``exp / log /
-sin / cos / tan / tanh / sinh / cosh / log1p / expm1 / pow`` are printed as
-calls of the deterministic implementations of ``csrc/sa_math.h`` (embedded
-into the generated header when used) instead of libm / ocml, so that host and
-device evaluate bit-identical arithmetic (both sides are compiled with
-``-ffp-contract=off``); this is what makes the step/order bookkeeping of the
+products, no ``fastmath`` style re-association is allowed, and the elementary and
+special functions are printed as calls of deterministic implementations
+(``sa_exp``, ``sa_asin``, ``sa_tgamma``, ``sa_bessel_j`` ...) instead of libm / ocml,
+so that host and device evaluate bit-identical arithmetic (both sides are compiled
+with ``-ffp-contract=off``); this is what makes the step/order bookkeeping of the
 HIP integrator comparable bit-for-bit with the CPU oracle -- for rational AND
-transcendental right-hand sides.  ``asin / acos / atan / atan2 / asinh / acosh /
-atanh / erf / erfc`` are printed the same way, as calls of ``csrc/sa_math_inv.h``:
-a second block, embedded after the first only when a callback calls one of its
-functions, so that the headers of models without them keep their text (and with
-it their cache keys and code objects).  ``gamma / loggamma / digamma / trigamma``
-(``polygamma(0, .)``, ``polygamma(1, .)``, ``factorial``) are calls of a third block,
-``csrc/sa_math_gamma.h``, embedded after the others under the same rule;
-``polygamma(n, .)`` with n >= 2 has no implementation and raises.  ``besselj / bessely /
-besseli / besselk`` of an integer literal order 0 ... ``SAM_BESSEL_NMAX`` are calls of a
-fourth block, ``csrc/sa_math_bessel.h`` (``sa_bessel_j(n, x)`` ...), embedded last under
-the same rule; a non-integer, symbolic or larger order raises.  Functions outside
-the four lists (``LIBM_ONLY``: cbrt, hypot, exp2, log2, log10) still compile, through
-libm / ocml, without the bit-equality guarantee; ``SympyProblem`` warns about them.
+transcendental right-hand sides.  The implementations live in the function blocks of
+``MATH_BLOCKS`` below, one ``csrc/sa_math*.h`` header each; the table names every
+function and the sympy class printed as it.  A block is embedded into a generated
+header in table order and only when a callback calls one of its functions (the first
+block whenever any is), so that the headers of models without them keep their text
+(and with it their cache keys and code objects).  ``polygamma(n, .)`` with n >= 2 and
+Bessel functions of a non-integer, symbolic or larger order than ``SAM_BESSEL_NMAX``
+have no implementation and raise.  Functions outside the table (``LIBM_ONLY``: cbrt,
+hypot, exp2, log2, log10) still compile, through libm / ocml, without the
+bit-equality guarantee; ``SympyProblem`` warns about them.
 
 Non-smooth forms: ``Abs / floor / Mod`` are printed by the inherited C99 printer as ``fabs / floor / fmod`` -- exact
 operations, the same bits on every implementation --, ``Piecewise`` and relations as nested ``?:`` selects,
@@ -61,7 +57,7 @@ from __future__ import annotations
 import hashlib
 import re
 from itertools import count
-from typing import Optional,  Dict, Iterable, List, Sequence, Tuple
+from typing import Optional,  Dict, Iterable, List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 import sympy as sym
@@ -333,84 +329,17 @@ class HipExprPrinter(C99CodePrinter):
             return "(1.0/sqrt(%s))" % self._print(base)
         return "sa_pow(%s, %s)" % (self._print(base), self._print(exp))
 
-    # transcendental functions: the deterministic implementations of csrc/sa_math.h (embedded into the generated
-    # header, MATH_C below), never libm / ocml -- device and oracle must round identically
+    # transcendental and special functions: the deterministic implementations of MATH_BLOCKS (embedded into the
+    # generated header), never libm / ocml -- device and oracle must round identically
     def _sa_call(self, name, expr):
         return "sa_%s(%s)" % (name, ", ".join(self._print(a) for a in expr.args))
-
-    def _print_exp(self, expr):
-        return self._sa_call("exp", expr)
 
     def _print_log(self, expr):
         if len(expr.args) == 2:      # log(x, base)
             return "(sa_log(%s)/sa_log(%s))" % (self._print(expr.args[0]), self._print(expr.args[1]))
         return self._sa_call("log", expr)
 
-    def _print_log1p(self, expr):
-        return self._sa_call("log1p", expr)
-
-    def _print_expm1(self, expr):
-        return self._sa_call("expm1", expr)
-
-    def _print_sin(self, expr):
-        return self._sa_call("sin", expr)
-
-    def _print_cos(self, expr):
-        return self._sa_call("cos", expr)
-
-    def _print_tan(self, expr):
-        return self._sa_call("tan", expr)
-
-    def _print_tanh(self, expr):
-        return self._sa_call("tanh", expr)
-
-    def _print_sinh(self, expr):
-        return self._sa_call("sinh", expr)
-
-    def _print_cosh(self, expr):
-        return self._sa_call("cosh", expr)
-
-    # inverse trigonometric / hyperbolic functions, erf, erfc: csrc/sa_math_inv.h (MATH_INV_C below)
-    def _print_asin(self, expr):
-        return self._sa_call("asin", expr)
-
-    def _print_acos(self, expr):
-        return self._sa_call("acos", expr)
-
-    def _print_atan(self, expr):
-        return self._sa_call("atan", expr)
-
-    def _print_atan2(self, expr):
-        return self._sa_call("atan2", expr)
-
-    def _print_asinh(self, expr):
-        return self._sa_call("asinh", expr)
-
-    def _print_acosh(self, expr):
-        return self._sa_call("acosh", expr)
-
-    def _print_atanh(self, expr):
-        return self._sa_call("atanh", expr)
-
-    def _print_erf(self, expr):
-        return self._sa_call("erf", expr)
-
-    def _print_erfc(self, expr):
-        return self._sa_call("erfc", expr)
-
-    # gamma family: csrc/sa_math_gamma.h (MATH_GAMMA_C below).  loggamma is printed as log|Gamma|, the real part:
-    # what C's lgamma and scipy.special.gammaln return
-    def _print_gamma(self, expr):
-        return self._sa_call("tgamma", expr)
-
-    def _print_loggamma(self, expr):
-        return self._sa_call("lgamma", expr)
-
-    def _print_digamma(self, expr):
-        return self._sa_call("digamma", expr)
-
-    def _print_trigamma(self, expr):
-        return self._sa_call("trigamma", expr)
+    # (the printers that are one plain call -- exp, asin, gamma -> tgamma ... -- are installed from MATH_BLOCKS below)
 
     def _print_polygamma(self, expr):
         order, u = expr.args
@@ -424,7 +353,7 @@ class HipExprPrinter(C99CodePrinter):
     def _print_factorial(self, expr):
         return "sa_tgamma(%s)" % self._print(expr.args[0] + 1)
 
-    # Bessel functions of integer order: csrc/sa_math_bessel.h (MATH_BESSEL_C below).  The order is printed as an
+    # Bessel functions of integer order: csrc/sa_math_bessel.h.  The order is printed as an
     # integer literal; sympy folds a negative integer order into a positive one itself, what is left of one goes
     # through J_-n = (-1)^n J_n, Y_-n = (-1)^n Y_n, I_-n = I_n, K_-n = K_n
     def _bessel_call(self, letter, expr, alternates):
@@ -493,6 +422,43 @@ class HipExprPrinter(C99CodePrinter):
         # the derivative of Heaviside / sign almost everywhere -- what sympy itself derives for the same switch written
         # as a Piecewise.  The jump term of the sensitivities is NOT carried (SympyProblem warns: delta_functions)
         return "0.0"
+
+
+class MathBlock(NamedTuple):
+    """One function block of the deterministic math library: a ``csrc/sa_math*.h`` header."""
+    name: str
+    header: str                             # file under csrc/
+    calls: Tuple[str, ...]                  # the functions sa_<call> of the header that generated text may call
+    printers: Tuple[Tuple[str, str], ...]   # (sympy function, call): printed as the plain call sa_<call>(args)
+
+    def called_in(self, text: str) -> bool:
+        return re.search(r"\bsa_(%s)\(" % "|".join(self.calls), text) is not None
+
+
+def _same(*names):
+    return tuple((name, name) for name in names)
+
+
+#: The function blocks, in the order they are embedded; every block after the first builds on the first (``inv`` on sa_exp,
+#: sa_log1p and the bit helpers, ``gamma`` and ``bessel`` on sa_exp, sa_log and the kernels of sa_log / sa_sin).  The
+#: functions without a printer here have a hand-written one in HipExprPrinter (Pow, log with a base, the reference's
+#: helpers; polygamma, factorial; the Bessel order handling).  loggamma is printed as log|Gamma|, the real part: what C's
+#: lgamma and scipy.special.gammaln return.
+MATH_BLOCKS = (
+    MathBlock("core", "sa_math.h",
+              ("exp", "expm1", "log", "log1p", "sin", "cos", "tan", "tanh", "sinh", "cosh", "pow", "logaddexp", "expit",
+               "dexpit", "cardinal_bspline4"),
+              _same("exp", "log1p", "expm1", "sin", "cos", "tan", "tanh", "sinh", "cosh")),
+    MathBlock("inv", "sa_math_inv.h", ("asin", "acos", "atan", "atan2", "asinh", "acosh", "atanh", "erf", "erfc"),
+              _same("asin", "acos", "atan", "atan2", "asinh", "acosh", "atanh", "erf", "erfc")),
+    MathBlock("gamma", "sa_math_gamma.h", ("lgamma", "tgamma", "digamma", "trigamma"),
+              (("gamma", "tgamma"), ("loggamma", "lgamma"), ("digamma", "digamma"), ("trigamma", "trigamma"))),
+    MathBlock("bessel", "sa_math_bessel.h", ("bessel_j", "bessel_y", "bessel_i", "bessel_k"), ()),
+)
+
+for _block in MATH_BLOCKS:
+    for _function, _call in _block.printers:
+        setattr(HipExprPrinter, "_print_" + _function, lambda self, expr, _call=_call: self._sa_call(_call, expr))
 
 
 #: callbacks with more output statements than this are emitted as a chain of chunk functions
@@ -1112,7 +1078,7 @@ def generate_problem_source(
         "#define SA_N_SUB %d" % n_sub,
         "#define SA_N_REM %d" % n_rem,
         HELPERS_C,
-        None,           # MATH_C, when a callback calls one of its functions
+        None,           # the blocks of MATH_BLOCKS that a callback calls a function of
         emit_function("sa_rhs", base, np.asarray(dydt, dtype=object).ravel(),
                       list(range(n)), n, symbol_map, "r_", matvec=mv("f"), leaf_axes=leaf_axes, out_array="SA_Y"),
         (emit_matfill_function("sa_jac", base, n, matfill["j"], symbol_map, "j_", "j") if "j" in matfill else
@@ -1134,113 +1100,64 @@ def generate_problem_source(
                       list(range(n_sub * n)), n_sub * n, symbol_map, "s_"),
         "",
     ]
-    uses_math = any(_MATH_CALL.search(part) for part in parts if part)
-    uses_inv = any(_MATH_INV_CALL.search(part) for part in parts if part)
-    uses_gamma = any(_MATH_GAMMA_CALL.search(part) for part in parts if part)
-    uses_bessel = any(_MATH_BESSEL_CALL.search(part) for part in parts if part)
-    parts[6] = (math_c() if uses_math or uses_inv or uses_gamma or uses_bessel
-                else "/* (no transcendental function: csrc/sa_math.h not embedded) */")
-    if uses_inv:                # the second block builds on the first (sa_exp, sa_log1p, the bit helpers)
-        parts[6] += "\n" + math_inv_c()
-    if uses_gamma:              # the third block builds on the first only (sa_exp, sa_log, the kernels of sa_log / sa_sin)
-        parts[6] += "\n" + math_gamma_c()
-    if uses_bessel:             # the fourth block builds on the first only (sa_exp, sa_log, the kernels of sa_sin)
-        parts[6] += "\n" + math_bessel_c()
+    used = [block for block in MATH_BLOCKS if any(block.called_in(part) for part in parts if part)]
+    if used:                    # in table order; the first block whenever any is: the others build on it
+        parts[6] = "\n".join(math_block_text(block.name) for block in MATH_BLOCKS if block in used or block is MATH_BLOCKS[0])
+    else:
+        parts[6] = "/* (no transcendental function: csrc/sa_math.h not embedded) */"
     if any(_MINMAX_CALL.search(part) for part in parts[7:] if part):
         parts[6] += "\n" + MINMAX_C
     return "\n".join(parts)
 
 
-#: a call of one of the deterministic functions of csrc/sa_math.h in generated text
-_MATH_CALL = re.compile(r"\bsa_(exp|expm1|log|log1p|sin|cos|tan|tanh|sinh|cosh|pow|logaddexp|expit|dexpit|"
-                        r"cardinal_bspline4)\(")
-#: ... and of csrc/sa_math_inv.h
-_MATH_INV_CALL = re.compile(r"\bsa_(asin|acos|atan|atan2|asinh|acosh|atanh|erf|erfc)\(")
-#: ... and of csrc/sa_math_gamma.h
-_MATH_GAMMA_CALL = re.compile(r"\bsa_(lgamma|tgamma|digamma|trigamma)\(")
-#: ... and of csrc/sa_math_bessel.h
-_MATH_BESSEL_CALL = re.compile(r"\bsa_bessel_(j|y|i|k)\(")
-#: ... and of MINMAX_C
+#: a call of MINMAX_C in generated text
 _MINMAX_CALL = re.compile(r"\bsa_(max|min)\(")
 #: functions the C99 printer would hand to libm / ocml (not bit-reproducible between host and device)
 LIBM_ONLY = ("cbrt", "exp2", "log2", "log10", "hypot")
 
 
-def _csrc(name: str) -> str:
+def math_block_text(name: str) -> str:
+    """Text of the header of the block ``name`` of MATH_BLOCKS."""
     import os
-    here = os.path.dirname(os.path.abspath(__file__))
-    with open(os.path.join(os.path.dirname(here), "csrc", name)) as fh:
+    header = {block.name: block.header for block in MATH_BLOCKS}[name]
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc", header)) as fh:
         return fh.read()
 
 
-def math_c() -> str:
-    """Text of csrc/sa_math.h (the deterministic exp / log / sin / pow ... shared by device and oracle)."""
-    return _csrc("sa_math.h")
+def math_boundaries(name: str) -> Dict[str, Tuple[float, ...]]:
+    """{function: the arguments at which its implementation changes interval / piece}, read from the ``SAM_<FN>_B<k>``
+    definitions of the header of the block ``name``, and what each block adds to them:
 
-
-def math_inv_c() -> str:
-    """Text of csrc/sa_math_inv.h (asin / acos / atan / atan2 / asinh / acosh / atanh / erf / erfc on the functions of
-    sa_math.h): embedded after ``math_c()`` in the headers that call one of them."""
-    return _csrc("sa_math_inv.h")
-
-
-def math_inv_boundaries() -> Dict[str, Tuple[float, ...]]:
-    """{function: the arguments at which its implementation changes interval}, read from the ``SAM_<FN>_B<k>``
-    definitions of csrc/sa_math_inv.h (erfc also changes where erf does above its own switch; atan2 changes where
-    atan does, in |y / x|)."""
+    ``inv``: erfc also changes where erf does above its own switch; atan2 changes where atan does, in |y / x|.
+    ``gamma``: an argument below the first boundary is shifted up by one, so lgamma / digamma / trigamma also change piece
+    at ``b - 1`` for the boundaries b in (B1, B1 + 1]; tgamma's recurrence changes its number of active stages at every
+    integer up to its boundary.
+    ``bessel``: ``j0, j1, y0, y1, i0, i1, k0, k1`` (the orders 0 and 1, in |x|) and ``jn, in`` (where an order >= 2 of J / I
+    changes method; J_n also changes the direction of its recurrence at |x| = n, and I above ``SAM_I_FAR`` takes the
+    exponential in two factors: that value is added to ``i0, i1, in``)."""
+    text = math_block_text(name)
     found: Dict[str, List[float]] = {}
-    for fn, value in re.findall(r"^#define SAM_([A-Z0-9]+)_B\d+ +(\S+)", math_inv_c(), re.M):
+    for fn, value in re.findall(r"^#define SAM_([A-Z0-9]+)_B\d+ +(\S+)", text, re.M):
         found.setdefault(fn.lower(), []).append(float(value))
-    found["erfc"] = found["erfc"] + [v for v in found["erf"] if v > max(found["erfc"])]
-    found["atan2"] = list(found["atan"])
+    if name == "inv":
+        found["erfc"] = found["erfc"] + [v for v in found["erf"] if v > max(found["erfc"])]
+        found["atan2"] = list(found["atan"])
+    elif name == "gamma":
+        for fn in ("lgamma", "digamma", "trigamma"):
+            first = min(found[fn])
+            found[fn] += [b - 1.0 for b in found[fn] if first < b <= first + 1.0 and b - 1.0 > 0.0 and b - 1.0 not in found[fn]]
+        stages = int(re.search(r"^#define SAM_TGAMMA_STAGES +(\d+)", text, re.M).group(1))
+        found["tgamma"] = [found["tgamma"][0] - k for k in range(stages)]
+    elif name == "bessel":
+        far = float(re.search(r"^#define SAM_I_FAR +(\S+)", text, re.M).group(1))
+        for fn in ("i0", "i1", "in"):
+            found[fn].append(far)
     return {fn: tuple(sorted(v)) for fn, v in found.items()}
-
-
-def math_gamma_c() -> str:
-    """Text of csrc/sa_math_gamma.h (lgamma / tgamma / digamma / trigamma on the functions of sa_math.h): embedded after
-    ``math_c()`` -- and after ``math_inv_c()`` where that is present -- in the headers that call one of them."""
-    return _csrc("sa_math_gamma.h")
-
-
-def math_gamma_boundaries() -> Dict[str, Tuple[float, ...]]:
-    """{function: the arguments y at which its implementation changes piece}, read from the ``SAM_<FN>_B<k>``
-    definitions of csrc/sa_math_gamma.h.  An argument below the first boundary is shifted up by one, so lgamma /
-    digamma / trigamma also change piece at ``b - 1`` for the boundaries b in (B1, B1 + 1]; tgamma's recurrence changes
-    its number of active stages at every integer up to its boundary."""
-    found: Dict[str, List[float]] = {}
-    for fn, value in re.findall(r"^#define SAM_([A-Z0-9]+)_B\d+ +(\S+)", math_gamma_c(), re.M):
-        found.setdefault(fn.lower(), []).append(float(value))
-    for fn in ("lgamma", "digamma", "trigamma"):
-        first = min(found[fn])
-        found[fn] += [b - 1.0 for b in found[fn] if first < b <= first + 1.0 and b - 1.0 > 0.0 and b - 1.0 not in found[fn]]
-    stages = int(re.search(r"^#define SAM_TGAMMA_STAGES +(\d+)", math_gamma_c(), re.M).group(1))
-    found["tgamma"] = [found["tgamma"][0] - k for k in range(stages)]
-    return {fn: tuple(sorted(v)) for fn, v in found.items()}
-
-
-def math_bessel_c() -> str:
-    """Text of csrc/sa_math_bessel.h (J_n / Y_n / I_n / K_n of integer order on the functions of sa_math.h): embedded
-    after the other blocks in the headers that call one of them."""
-    return _csrc("sa_math_bessel.h")
 
 
 def math_bessel_nmax() -> int:
     """The largest order csrc/sa_math_bessel.h implements (its ``SAM_BESSEL_NMAX``)."""
-    return int(re.search(r"^#define SAM_BESSEL_NMAX +(\d+)", math_bessel_c(), re.M).group(1))
-
-
-def math_bessel_boundaries() -> Dict[str, Tuple[float, ...]]:
-    """{function: the arguments |x| at which its implementation changes piece}, read from the ``SAM_<FN>_B<k>``
-    definitions of csrc/sa_math_bessel.h: ``j0, j1, y0, y1, i0, i1, k0, k1`` (the orders 0 and 1) and ``jn, in`` (where
-    an order >= 2 of J / I changes method; J_n also changes the direction of its recurrence at |x| = n, and I above
-    ``SAM_I_FAR`` takes the exponential in two factors: that value is added to ``i0, i1, in``)."""
-    found: Dict[str, List[float]] = {}
-    for fn, value in re.findall(r"^#define SAM_([A-Z0-9]+)_B\d+ +(\S+)", math_bessel_c(), re.M):
-        found.setdefault(fn.lower(), []).append(float(value))
-    far = float(re.search(r"^#define SAM_I_FAR +(\S+)", math_bessel_c(), re.M).group(1))
-    for fn in ("i0", "i1", "in"):
-        found[fn].append(far)
-    return {fn: tuple(sorted(v)) for fn, v in found.items()}
+    return int(re.search(r"^#define SAM_BESSEL_NMAX +(\d+)", math_block_text("bessel"), re.M).group(1))
 
 
 def libm_calls(source: str) -> List[str]:

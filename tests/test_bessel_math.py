@@ -20,6 +20,7 @@ The GPU half (device == oracle bit for bit, device vs truth) is tests/test_gpu_b
 import ctypes
 import functools
 import hashlib
+import json
 import os
 import subprocess
 import sys
@@ -28,6 +29,7 @@ import warnings
 import numpy as np
 import pytest
 
+from tests.family_checks import compile_math_blocks
 from tests.helpers import make_oracle, make_problem
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,40 +49,15 @@ HIGHER_ORDER_CEILING = {
     ("i", "10^U(-300,0)"): 5, ("i", "U(0,30)"): 14, ("i", "U(30,713)"): 6,
     ("k", "10^U(-300,0)"): 13, ("k", "U(0,30)"): 10, ("k", "U(30,745)"): 6,
 }
-#: sha256(native_source()) on the parent commit: the headers of models without Bessel functions keep their text
-PARENT_SOURCE_SHA256 = {
-    "lv": "7c42589f524cdb9cfc96bfe23774b39f1eb57d9d4888d137e0f91578af2b0584",
-    "misc": "9fdaca219d8ea8b6e213a6eed4156e6eb42575938d75ba22ccb77aaac96fdf96",
-    "forcing": "10e8cb99c7496147e58269b72aaf0d94f9f679d197ab23ab65061d27c809c838",
-    "logistic_switch": "b3ed00cca45bbabc911265224079000cc991d4f9e983fa9fe72150bee1f46046",
-    "mathfn_a": "4de0297e3f2cc6d7fadd661072856a56aecb12ca695eb0038b6e63fdb29c3ecb",
-    "mathfn_c": "349c6aa2ebfb561938c26549129d30a7c6a60905b9361f8248155621b70b9447",
-    "mathfn_e": "67fc0c0b6b6799962a4b1cd34758bb7ada2fa42cd9adf4a88f897789ecb28b37",
-    "probit_gate": "48fa2a939ca8e3026028e864a6d22f7e010396d464cd5c2b5eacb127b72d7831",
-    "gamma_delay": "d2b8b07f53bd64431d287d5f7e61ec71b97c263e7ee1b4f9142caaf258c32103",
-}
 
 
 @pytest.fixture(scope="module")
 def mathlib():
     """sa_math.h + sa_math_bessel.h compiled for the host exactly like the oracle compiles a generated header;
     ``call(family, order, x)``."""
-    hdrs = [os.path.join(ROOT, "sunode_amd", "csrc", f) for f in ("sa_math.h", "sa_math_bessel.h")]
-    key = hashlib.sha256(b"".join(open(h, "rb").read() for h in hdrs)).hexdigest()[:12]
-    out = os.path.join(ROOT, "oracle", "_build", "sa_math_bessel_%s.so" % key)
-    if not os.path.exists(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        src = ["#include <math.h>", "#define SA_FN static inline"] + ['#include "%s"' % h for h in hdrs]
-        src += ["void w_%s(int n, int order, const double *x, double *o) "
-                "{ for (int i = 0; i < n; i++) o[i] = sa_bessel_%s(order, x[i]); }" % (f, f) for f in FAMILIES]
-        c = out[:-3] + ".c"
-        with open(c, "w") as fh:
-            fh.write("\n".join(src) + "\n")
-        with open("/proc/cpuinfo") as fh:
-            fma = ["-mfma"] if " fma " in fh.read() else []
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11"] + fma +
-                       [c, "-o", out, "-lm"], check=True, capture_output=True, text=True)
-    L = ctypes.CDLL(out)
+    L = compile_math_blocks(("core", "bessel"), [
+        "void w_%s(int n, int order, const double *x, double *o) "
+        "{ for (int i = 0; i < n; i++) o[i] = sa_bessel_%s(order, x[i]); }" % (f, f) for f in FAMILIES])
 
     def call(name, order, x):
         x = np.ascontiguousarray(x, float)
@@ -313,9 +290,9 @@ def _check_around(mathlib, name, n, b):
 
 
 def test_both_sides_of_every_piece_boundary(mathlib):
-    """The boundaries come from the header's own definitions (codegen.math_bessel_boundaries)."""
+    """The boundaries come from the header's own definitions (codegen.math_boundaries("bessel"))."""
     from sunode_amd.symode import codegen
-    bounds = codegen.math_bessel_boundaries()
+    bounds = codegen.math_boundaries("bessel")
     assert set(bounds) == {"j0", "j1", "y0", "y1", "i0", "i1", "k0", "k1", "jn", "in"}
     assert len(bounds["j0"]) == 4 and len(bounds["y0"]) == 6 and len(bounds["i0"]) == 3 and len(bounds["k0"]) == 5
     assert len(bounds["in"]) == 3 and len(bounds["jn"]) == 1
@@ -469,11 +446,13 @@ def test_the_block_comes_after_the_other_blocks():
             < src.index("#endif /* SA_MATH_GAMMA_H */") < src.index("#ifndef SA_MATH_BESSEL_H"))
 
 
-def test_existing_headers_keep_their_text():
-    for name, digest in PARENT_SOURCE_SHA256.items():
+def test_existing_headers_keep_their_text(golden_dir):
+    with open(os.path.join(golden_dir, "native_source_sha256.json")) as fh:
+        digests = json.load(fh)
+    for name in ("lv", "misc", "forcing", "logistic_switch", "mathfn_a", "mathfn_c", "mathfn_e", "probit_gate", "gamma_delay"):
         src = make_problem(name).native_source()
         assert "SA_HAVE_MATH_BESSEL" not in src
-        assert hashlib.sha256(src.encode()).hexdigest() == digest, name
+        assert hashlib.sha256(src.encode()).hexdigest() == digests[name], name
 
 
 def test_host_helpers_agree_with_scipy():
@@ -596,7 +575,7 @@ def test_truth_draws_cross_piece_boundaries_and_a_zero_of_j0(golden_dir):
     from sunode_amd.symode import codegen
     d = np.load(os.path.join(golden_dir, "truth_bessel_ring.npz"))
     assert d["y0"].shape[0] == 16
-    bounds = np.array(codegen.math_bessel_boundaries()["j0"])
+    bounds = np.array(codegen.math_boundaries("bessel")["j0"])
     zeros = np.array([2.404825557695773, 5.520078110286311, 8.653727912911013])
     for i in range(16):
         lo, hi = d["ps"][i, 1] * d["tvals"][0], d["ps"][i, 1] * d["tvals"][-1]

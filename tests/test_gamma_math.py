@@ -20,13 +20,14 @@ The GPU half (device == oracle bit for bit, device vs truth) is tests/test_gpu_g
 """
 import ctypes
 import hashlib
+import json
 import os
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
+from tests.family_checks import compile_math_blocks
 from tests.helpers import make_oracle, make_problem
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,38 +35,15 @@ FOUR = ["lgamma", "tgamma", "digamma", "trigamma"]
 ULP_CEILING = 4.0
 N_POINTS = 1500
 PSI_ROOT = 1.4616321449683622            # the positive root of digamma
-#: sha256(native_source()) on the parent commit: the headers of models without the gamma family keep their text
-PARENT_SOURCE_SHA256 = {
-    "lv": "7c42589f524cdb9cfc96bfe23774b39f1eb57d9d4888d137e0f91578af2b0584",
-    "misc": "9fdaca219d8ea8b6e213a6eed4156e6eb42575938d75ba22ccb77aaac96fdf96",
-    "forcing": "10e8cb99c7496147e58269b72aaf0d94f9f679d197ab23ab65061d27c809c838",
-    "logistic_switch": "b3ed00cca45bbabc911265224079000cc991d4f9e983fa9fe72150bee1f46046",
-    "mathfn_a": "4de0297e3f2cc6d7fadd661072856a56aecb12ca695eb0038b6e63fdb29c3ecb",
-    "mathfn_c": "349c6aa2ebfb561938c26549129d30a7c6a60905b9361f8248155621b70b9447",
-    "probit_gate": "48fa2a939ca8e3026028e864a6d22f7e010396d464cd5c2b5eacb127b72d7831",
-}
 
 
 @pytest.fixture(scope="module")
 def mathlib():
     """sa_math.h + sa_math_inv.h + sa_math_gamma.h compiled for the host exactly like the oracle compiles a generated
     header."""
-    hdrs = [os.path.join(ROOT, "sunode_amd", "csrc", f) for f in ("sa_math.h", "sa_math_inv.h", "sa_math_gamma.h")]
-    key = hashlib.sha256(b"".join(open(h, "rb").read() for h in hdrs)).hexdigest()[:12]
-    out = os.path.join(ROOT, "oracle", "_build", "sa_math_gamma_%s.so" % key)
-    if not os.path.exists(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        src = ["#include <math.h>", "#define SA_FN static inline"] + ['#include "%s"' % h for h in hdrs]
-        src += ["void w_%s(int n, const double *x, double *o) { for (int i = 0; i < n; i++) o[i] = sa_%s(x[i]); }"
-                % (f, f) for f in FOUR]
-        c = out[:-3] + ".c"
-        with open(c, "w") as fh:
-            fh.write("\n".join(src) + "\n")
-        with open("/proc/cpuinfo") as fh:
-            fma = ["-mfma"] if " fma " in fh.read() else []
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11"] + fma +
-                       [c, "-o", out, "-lm"], check=True, capture_output=True, text=True)
-    L = ctypes.CDLL(out)
+    L = compile_math_blocks(("core", "inv", "gamma"), [
+        "void w_%s(int n, const double *x, double *o) { for (int i = 0; i < n; i++) o[i] = sa_%s(x[i]); }" % (f, f)
+        for f in FOUR])
 
     def call(name, x):
         x = np.ascontiguousarray(x, float)
@@ -224,11 +202,11 @@ def test_special_values(mathlib):
 
 
 def test_both_sides_of_every_piece_boundary(mathlib):
-    """The boundaries come from the header's own definitions (codegen.math_gamma_boundaries): 41 consecutive doubles
+    """The boundaries come from the header's own definitions (codegen.math_boundaries("gamma")): 41 consecutive doubles
     around each one -- and around its mirror image on the negative axis where that is not a pole (lgamma reflects to
     -x) -- stay within the ceilings of the accuracy test."""
     from sunode_amd.symode import codegen
-    bounds = codegen.math_gamma_boundaries()
+    bounds = codegen.math_boundaries("gamma")
     assert set(bounds) == set(FOUR)
     assert len(bounds["lgamma"]) >= 5 and len(bounds["tgamma"]) == 6 and len(bounds["digamma"]) == 4 and len(bounds["trigamma"]) == 4
     for name, bs in bounds.items():
@@ -278,11 +256,13 @@ def test_the_block_comes_after_the_inverse_block_where_both_are_present():
     assert src.index("#endif /* SA_MATH_H */") < src.index("#endif /* SA_MATH_INV_H */") < src.index("#ifndef SA_MATH_GAMMA_H")
 
 
-def test_existing_headers_keep_their_text():
-    for name, digest in PARENT_SOURCE_SHA256.items():
+def test_existing_headers_keep_their_text(golden_dir):
+    with open(os.path.join(golden_dir, "native_source_sha256.json")) as fh:
+        digests = json.load(fh)
+    for name in ("lv", "misc", "forcing", "logistic_switch", "mathfn_a", "mathfn_c", "probit_gate"):
         src = make_problem(name).native_source()
         assert "SA_HAVE_MATH_GAMMA" not in src
-        assert hashlib.sha256(src.encode()).hexdigest() == digest, name
+        assert hashlib.sha256(src.encode()).hexdigest() == digests[name], name
 
 
 def test_polygamma_beyond_trigamma_raises():

@@ -12,15 +12,13 @@ import functools
 import numpy as np
 import pytest
 
+from tests.family_checks import CMP, CMP_B, TOL
 from tests.helpers import make_oracle, make_problem
 from tests.test_nonsmooth import KEYS, TRUTH_BARS, points
-from tools.problems import kinked_batch, threshold_sir_batch
+from tools.family_models import FAMILY
+from tools.problems import kinked_batch
 
 pytestmark = pytest.mark.gpu
-
-CMP = [0, 1, 2, 3, 4, 5, 6, 7, 8]
-CMP_B = [0, 1, 2, 3, 4, 5, 6, 9, 10, 12]
-TOL = dict(abstol=1e-8, reltol=1e-8, backward_abstol=1e-8, backward_reltol=1e-8, quad_abstol=1e-8, quad_reltol=1e-8)
 
 
 def assert_same_bits(got, want, what=""):
@@ -31,16 +29,10 @@ def assert_same_bits(got, want, what=""):
     assert not differ.any(), (what, np.argwhere(differ)[:8].tolist(), got[differ][:8], want[differ][:8])
 
 
-def _batch(name, B):
-    if name == "kinked":
-        return kinked_batch(B)
-    return threshold_sir_batch(B, int(name[len("threshold_sir"):]))
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle_run(name, B, hermite=False):
     """Forward + adjoint of the B-draw batch in the oracle (computed once per model, batch size and interpolation)."""
-    d = _batch(name, B)
+    d = FAMILY[name].batch(B)
     orc = make_oracle(name)
     cfg = orc.config(rtol=1e-8, atol=1e-8, rtolB=1e-8, atolB=1e-8, rtolQB=1e-8, atolQB=1e-8, hermite=hermite)
     tv = d["tvals"]
@@ -117,7 +109,7 @@ def test_model_callbacks_equal_the_oracle_bitwise(name):
         assert got["codes"][i].tolist() == np.asarray(host["codes"]).tolist()
 
 
-@pytest.mark.parametrize("group", [None, "wave4", "wave8", "wave", "mem"])
+@pytest.mark.parametrize("group", [None] + list(FAMILY["kinked"].mappings))
 def test_kinked_forward_adjoint_in_every_mapping(group, monkeypatch):
     """B = 37 (no multiple of a group size; draws cross the three surfaces at times spread over many steps, a fifth
     never reach one): statuses, every statistic, states, gradients and lamda equal the oracle's bit for bit."""
@@ -155,7 +147,8 @@ def test_kinked_matches_truth(golden_dir):
     _against_truth("kinked", golden_dir)
 
 
-@pytest.mark.parametrize("M,group", [(4, None), (4, "wave8"), (8, None), (8, "wave"), (16, None), (16, "wave"), (16, "mem")])
+@pytest.mark.parametrize("M,group", [(M, group) for M in (4, 8, 16)
+                                     for group in [None] + list(FAMILY["threshold_sir%d" % M].mappings)])
 def test_threshold_sir_lanes_on_different_branches(M, group, monkeypatch):
     """B = 21; in every instance some groups start above the threshold and some below (and above / below the saturation
     level of the recovery): lanes of one instance are on different branches inside SA_FAM_BEGIN (M = 4: lean 4-lane

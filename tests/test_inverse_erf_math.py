@@ -12,14 +12,13 @@
 The GPU half (device == oracle bit for bit, device vs truth) is tests/test_gpu_inverse_erf.py.
 """
 import ctypes
-import hashlib
 import os
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
+from tests.family_checks import compile_math_blocks
 from tests.helpers import make_oracle, make_problem
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,24 +31,10 @@ TINY = 2.2250738585072014e-308          # smallest normal double
 @pytest.fixture(scope="module")
 def mathlib():
     """sa_math.h + sa_math_inv.h compiled for the host exactly like the oracle compiles a generated header."""
-    hdrs = [os.path.join(ROOT, "sunode_amd", "csrc", f) for f in ("sa_math.h", "sa_math_inv.h")]
-    key = hashlib.sha256(b"".join(open(h, "rb").read() for h in hdrs)).hexdigest()[:12]
-    out = os.path.join(ROOT, "oracle", "_build", "sa_math_inv_%s.so" % key)
-    if not os.path.exists(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        src = ["#include <math.h>", "#define SA_FN static inline"] + ['#include "%s"' % h for h in hdrs]
-        src += ["void w_%s(int n, const double *x, double *o) { for (int i = 0; i < n; i++) o[i] = sa_%s(x[i]); }"
-                % (f, f) for f in ONE]
-        src += ["void w_atan2(int n, const double *y, const double *x, double *o) "
-                "{ for (int i = 0; i < n; i++) o[i] = sa_atan2(y[i], x[i]); }"]
-        c = out[:-3] + ".c"
-        with open(c, "w") as fh:
-            fh.write("\n".join(src) + "\n")
-        with open("/proc/cpuinfo") as fh:
-            fma = ["-mfma"] if " fma " in fh.read() else []
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11"] + fma +
-                       [c, "-o", out, "-lm"], check=True, capture_output=True, text=True)
-    L = ctypes.CDLL(out)
+    L = compile_math_blocks(("core", "inv"), [
+        "void w_%s(int n, const double *x, double *o) { for (int i = 0; i < n; i++) o[i] = sa_%s(x[i]); }" % (f, f)
+        for f in ONE] + ["void w_atan2(int n, const double *y, const double *x, double *o) "
+                         "{ for (int i = 0; i < n; i++) o[i] = sa_atan2(y[i], x[i]); }"])
 
     def call(name, x, y=None):
         x = np.ascontiguousarray(x, float)
@@ -166,11 +151,11 @@ def test_special_values(mathlib):
 
 
 def test_both_sides_of_every_interval_boundary(mathlib):
-    """The boundaries come from the header's own definitions (codegen.math_inv_boundaries): 41 consecutive doubles
+    """The boundaries come from the header's own definitions (codegen.math_boundaries("inv")): 41 consecutive doubles
     around each one, and around its mirror image for the odd / two-sided functions, stay within the ulp ceiling."""
     from sunode_amd.symode import codegen
     mp = _mp()
-    bounds = codegen.math_inv_boundaries()
+    bounds = codegen.math_boundaries("inv")
     assert set(bounds) == set(NINE) and all(len(b) >= 1 for b in bounds.values())
     assert len(bounds["atan"]) == 4 and len(bounds["erf"]) == 5 and len(bounds["erfc"]) >= 6
     for name, bs in bounds.items():

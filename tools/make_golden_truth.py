@@ -15,9 +15,8 @@ Independent oracles for the integrator half:
 
 Usage: python tools/make_golden_truth.py   (a few minutes; outputs are committed)
        python tools/make_golden_truth.py --times    (only truth_times_<name>.npz: see ``times_truth``)
-       python tools/make_golden_truth.py --inverse-erf    (only truth_probit_gate.npz: see ``inverse_erf_truth``)
-       python tools/make_golden_truth.py --gamma    (only truth_gamma_delay.npz: see ``gamma_truth``)
-       python tools/make_golden_truth.py --bessel    (only truth_bessel_ring.npz: see ``bessel_truth``)
+       python tools/make_golden_truth.py --transcendental | --inverse-erf | --gamma | --bessel
+                                                    (only the fixtures of that family: see ``FAMILY_FLAGS``, ``family_truth``)
        python tools/make_golden_truth.py --nonsmooth    (only truth_kinked.npz, truth_threshold_sir8.npz: see ``nonsmooth_truth``)
 """
 from __future__ import annotations
@@ -35,9 +34,9 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 from sunode_amd import SympyProblem  # noqa: E402
 from sunode_amd.symode.problem import HOST_FUNCTIONS  # noqa: E402
-from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, bessel_ring_batch, forcing_batch, logistic_switch_batch, lv_batch,  # noqa: E402
-                            gamma_delay_batch, kinked_batch, misc_batch, probit_gate_batch, robertson_batch, seir_batch,
-                            threshold_sir_batch)
+from tools.family_models import FAMILY  # noqa: E402
+from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, forcing_batch, lv_batch, misc_batch,  # noqa: E402
+                            robertson_batch, seir_batch)
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -122,49 +121,22 @@ def dvode_run(f, jac, y0, tvals, rtol, atol, args):
                 nni=int(iw[19]), ncfn=int(iw[20]), netf=int(iw[21]), y=np.array(ys).tolist())
 
 
-def transcendental_truth():
-    """truth_<name>.npz for the models with transcendental right-hand sides (8 draws each, per-instance cotangents):
-    ``forcing`` (expit / logaddexp / spline input -- the B-spline evaluated by the Cox-de Boor recursion, i.e. NOT by
-    the polynomial pieces the generated code shares with the reference), ``logistic_switch``, ``misc``."""
-    for name, batch in (("forcing", forcing_batch), ("logistic_switch", logistic_switch_batch), ("misc", misc_batch)):
-        prob = make(name)
-        d = batch(8)
-        y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
-        np.savez(os.path.join(GOLD, "truth_%s.npz" % name), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
-                 tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
-
-
-def inverse_erf_truth():
-    """truth_probit_gate.npz: 16 draws of ``probit_gate`` (erf / erfc / asin / acos / atan / atan2 / asinh / acosh /
-    atanh in one right-hand side; the host functions are numpy's and scipy.special's erf / erfc -- nothing of
-    csrc/sa_math_inv.h is on this side)."""
-    prob = make("probit_gate")
-    d = probit_gate_batch(16)
+def family_truth(name):
+    """truth_<name>.npz of an integrated model of a smooth function family (tools/family_models.py: its batch and number
+    of draws, per-instance cotangents).  Nothing of csrc/sa_math*.h is on this side: the host functions are numpy's and
+    scipy.special's (erf / erfc; gammaln / gamma / digamma / polygamma; jv / yv / iv / kv), and the B-spline of ``forcing``
+    is evaluated by the Cox-de Boor recursion, NOT by the polynomial pieces the generated code shares with the
+    reference."""
+    prob = make(name)
+    d = FAMILY[name].batch(FAMILY[name].truth_draws)
     y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
-    np.savez(os.path.join(GOLD, "truth_probit_gate.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
+    np.savez(os.path.join(GOLD, "truth_%s.npz" % name), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
              tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
 
 
-def gamma_truth():
-    """truth_gamma_delay.npz: 16 draws of ``gamma_delay`` (loggamma / gamma / digamma of states and of the inferred
-    shape; their derivatives through polygamma; the host functions are scipy.special's gammaln / gamma / digamma /
-    polygamma -- nothing of csrc/sa_math_gamma.h is on this side)."""
-    prob = make("gamma_delay")
-    d = gamma_delay_batch(16)
-    y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
-    np.savez(os.path.join(GOLD, "truth_gamma_delay.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
-             tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
-
-
-def bessel_truth():
-    """truth_bessel_ring.npz: 16 draws of ``bessel_ring`` (I1 / I0 of a state, J0 of an inferred wavenumber times t, K0
-    and Y0 of the states; their derivatives through the neighbouring orders; the host functions are scipy.special's
-    jv / yv / iv / kv -- nothing of csrc/sa_math_bessel.h is on this side)."""
-    prob = make("bessel_ring")
-    d = bessel_ring_batch(16)
-    y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853")
-    np.savez(os.path.join(GOLD, "truth_bessel_ring.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
-             tvals=d["tvals"], grads=d["grads"], y_out=y_out, grad_params=gp, grad_y0=gy0)
+#: command-line flag -> the models whose truth ``family_truth`` writes
+FAMILY_FLAGS = {"--transcendental": ("forcing", "logistic_switch", "misc"), "--inverse-erf": ("probit_gate",),
+                "--gamma": ("gamma_delay",), "--bessel": ("bessel_ring",)}
 
 
 #: what the two DOP853 runs of ``nonsmooth_truth`` (rtol 1e-13 and 1e-11) must agree to, in the tests' own error
@@ -193,9 +165,9 @@ def nonsmooth_truth():
     (stored) and at 1e-11 -- and the two must agree to ``NONSMOOTH_AGREE``, a hundredth of the bars the tests apply; the
     measured agreement is stored next to the truth (``agree_<quantity>``).  ``kinked`` also stores the forward
     sensitivities dy/dp [B, n_t, p, n]."""
-    for name, batch in (("kinked", kinked_batch), ("threshold_sir8", lambda B: threshold_sir_batch(B, 8))):
+    for name in ("kinked", "threshold_sir8"):
         prob = make(name)
-        d = batch(8)
+        d = FAMILY[name].batch(FAMILY[name].truth_draws)
         runs = []
         for rtol, atol in ((1e-13, 1e-15), (1e-11, 1e-13)):
             y_out, gp, gy0, sens = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], d["grads"], "DOP853",
@@ -364,21 +336,14 @@ def main():
     if "--times" in sys.argv:
         times_truth()
         return
-    if "--transcendental" in sys.argv:          # only the round-6 fixtures (the others are unchanged)
-        transcendental_truth()
-        return
     if "--sweep" in sys.argv:
         sweep_truth()
         return
-    if "--inverse-erf" in sys.argv:
-        inverse_erf_truth()
-        return
-    if "--gamma" in sys.argv:
-        gamma_truth()
-        return
-    if "--bessel" in sys.argv:
-        bessel_truth()
-        return
+    for flag, models in FAMILY_FLAGS.items():
+        if flag in sys.argv:
+            for name in models:
+                family_truth(name)
+            return
     if "--nonsmooth" in sys.argv:
         nonsmooth_truth()
         return
@@ -469,10 +434,9 @@ def main():
     y_out, gp, gy0 = truth_batch(prob, d["y0"], d["ps"], d["pr"], d["t0"], d["tvals"], g, "DOP853")
     np.savez(os.path.join(GOLD, "truth_seir.npz"), y0=d["y0"], ps=d["ps"], pr=d["pr"], t0=d["t0"],
              tvals=d["tvals"], grads=g, y_out=y_out, grad_params=gp, grad_y0=gy0)
-    transcendental_truth()
-    inverse_erf_truth()
-    gamma_truth()
-    bessel_truth()
+    for models in FAMILY_FLAGS.values():
+        for name in models:
+            family_truth(name)
     nonsmooth_truth()
     sweep_truth()
     print("done")

@@ -17,8 +17,7 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _DIR = os.path.join(ROOT, "sunode_amd", "_cache", "problems")
 _SOURCES = ["tools/problems.py", "sunode_amd/symode/problem.py", "sunode_amd/symode/codegen.py",
-            "sunode_amd/symode/lambdify.py", "sunode_amd/csrc/sa_math.h", "sunode_amd/csrc/sa_math_inv.h",
-            "sunode_amd/csrc/sa_math_gamma.h", "sunode_amd/csrc/sa_math_bessel.h", "sunode_amd/dtypesubset.py"]
+            "sunode_amd/symode/lambdify.py", "sunode_amd/dtypesubset.py"]       # ... and the headers of codegen.MATH_BLOCKS
 
 
 def spec_of(name):
@@ -38,8 +37,9 @@ def spec_of(name):
 
 @functools.lru_cache(maxsize=None)
 def _source_key():
+    from sunode_amd.symode.codegen import MATH_BLOCKS
     h = hashlib.sha256()
-    for rel in _SOURCES:
+    for rel in _SOURCES + ["sunode_amd/csrc/" + block.header for block in MATH_BLOCKS]:
         with open(os.path.join(ROOT, rel), "rb") as fh:
             h.update(fh.read())
     import sympy
