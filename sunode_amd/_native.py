@@ -287,9 +287,29 @@ def _size_defines(native_source: str):
     return ["-DSA_BUILD_NS=%d" % n, "-DSA_BUILD_NQ=%d" % p] + os.environ.get("SA_KERNEL_DEFINES", "").split()
 
 
+def _band_widths(native_source: str, fname: str, band):
+    """(ml, mu) of a band build (``band`` = (lower, upper) bandwidth of the Jacobian), clamped to n - 1, or None: only
+    the memory-resident mapping carries the band LU, and a missing kernel is an error."""
+    import re
+    if band is None:
+        return None
+    if fname != "bdf_mem.hip":
+        raise NativeBuildError("band=%r: only the memory-resident mapping (bdf_mem.hip) has a band LU, this build "
+                               "is %s" % (band, fname))
+    n = int(re.search(r"#define SA_N_STATES (\d+)", native_source).group(1))
+    ml, mu = (int(w) for w in band)
+    if ml < 0 or mu < 0:
+        raise ValueError("band widths must not be negative: %r" % (band,))
+    return min(ml, max(n - 1, 0)), min(mu, max(n - 1, 0))
+
+
 def code_object_path(native_source: str, sens: bool = False, constraints: bool = False,
-                     hermite: bool = False, compact: bool = False, safe: bool = False, group: Optional[str] = None) -> str:
+                     hermite: bool = False, compact: bool = False, safe: bool = False, group: Optional[str] = None,
+                     band=None) -> str:
+    """``band`` = (ml, mu): the band build of the memory-resident mapping (-DSA_BAND_ML / -DSA_BAND_MU); the key carries
+    a BAND tag only when it is set, so every other build keeps its key."""
     fname, group = kernel_variant(native_source, sens, constraints, hermite, group=group)
+    band = _band_widths(native_source, fname, band)
     kern = os.path.join(_CSRC, fname)
     deps = [kern] + [os.path.join(_CSRC, f) for f in ("sa_device_abi.h", "sa_common.h", "bdf_core.h")]
     deps = [d for d in deps if os.path.exists(d)]
@@ -299,7 +319,8 @@ def code_object_path(native_source: str, sens: bool = False, constraints: bool =
              + b"G%d" % group + fname.encode()
              + os.environ.get("SA_KERNEL_DEFINES", "").encode() + os.environ.get("SA_WAVES_PER_EU", "").encode()
              + (b"SENS" if sens else b"") + (b"CONSTR" if constraints else b"") + (b"HERMITE" if hermite else b"")
-             + (b"COMPACT" if compact else b""))
+             + (b"COMPACT" if compact else b"")
+             + (b"BAND%d_%d" % band if band is not None else b""))
     key = _hash_files(*deps, extra=extra) if os.path.exists(kern) else \
         hashlib.sha256(extra).hexdigest()[:16]
     return os.path.join(_CACHE, "sa_%s.hsaco" % key)
@@ -307,17 +328,21 @@ def code_object_path(native_source: str, sens: bool = False, constraints: bool =
 
 def build_code_object(native_source: str, force: bool = False, keep_temps: bool = False,
                       sens: bool = False, constraints: bool = False, hermite: bool = False, compact: bool = False,
-                      safe: bool = False, group: Optional[str] = None) -> str:
+                      safe: bool = False, group: Optional[str] = None, band=None) -> str:
     """Compile the integrator kernels for one problem to a gfx950 code object (cached).
     ``constraints=True`` builds the variant that enforces CVodeSetConstraints-style inequality
     constraints (a separate code object: the default build carries no trace of them).
     ``safe=True``: the CONSERVATIVE build -- same source, same defines, same flags, plus SAFETY_CODEGEN_FLAGS
-    (SIOptimizeVGPRLiveRange off): the partner of the default build in the differential guard (NativeSolver)."""
+    (SIOptimizeVGPRLiveRange off): the partner of the default build in the differential guard (NativeSolver).
+    ``band=(ml, mu)``: band storage and band LU of the Newton matrix in the memory-resident mapping (csrc/bdf_mem.hip,
+    SA_BAND_ML / SA_BAND_MU: a separate code object); the caller vouches that the Jacobian has no entry outside it."""
     os.makedirs(_CACHE, exist_ok=True)
-    out = code_object_path(native_source, sens, constraints, hermite, compact, safe, group)
+    out = code_object_path(native_source, sens, constraints, hermite, compact, safe, group, band)
     if os.path.exists(out) and not force:
         return out
     fname, group = kernel_variant(native_source, sens, constraints, hermite, group=group)
+    band = _band_widths(native_source, fname, band)
+    band_defines = ["-DSA_BAND_ML=%d" % band[0], "-DSA_BAND_MU=%d" % band[1]] if band is not None else []
     kern = os.path.join(_CSRC, fname)
     hdr = out[:-6] + ".h"
     with open("%s.tmp%d" % (hdr, os.getpid()), "w") as fh:      # (concurrent ranks: private temporaries, atomic renames)
@@ -331,7 +356,7 @@ def build_code_object(native_source: str, force: bool = False, keep_temps: bool 
               "-Xclang", "-disable-O0-optnone", "-ffp-contract=off", "-std=c++17",
               "-DSA_PROBLEM_HEADER=\"%s\"" % hdr, "-DSA_GROUP=%d" % group] + _size_defines(native_source)
              + (["-DSA_SENS=1"] if sens else []) + (["-DSA_CONSTRAINTS=1"] if constraints else [])
-             + (["-DSA_HERMITE=1"] if hermite else []) + (["-DSA_COMPACT_TRAJ=1"] if compact else [])
+             + (["-DSA_HERMITE=1"] if hermite else []) + (["-DSA_COMPACT_TRAJ=1"] if compact else []) + band_defines
              + ["-I" + _CSRC, kern, "-o", bc0])
         _run([os.path.join(LLVM_BIN, "opt"), "-passes=always-inline,sroa", bc0, "-o", bc1])
         occupancy = os.environ.get("SA_WAVES_PER_EU")
@@ -401,6 +426,31 @@ def code_object_notes(path: str) -> dict:
                 row[f] = int(m.group(1))
         out[name.group(1)] = row
     return out
+
+
+def code_object_meta(path: str) -> dict:
+    """The ``sa_meta`` record of a code object, read from the file (no GPU): n_states, n_sub, n_rem, abi, lanes per
+    instance and ``ws_doubles``, the per-instance workspace the host library allocates for it."""
+    import struct
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if data[:6] != b"\x7fELF\x02\x01":
+        raise ValueError("%s is not a little-endian ELF64 file" % path)
+    shoff, = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + k * shentsize) for k in range(shnum)]
+    for _name, stype, _flags, _addr_, off, size, link, _info, _align, entsize in sections:
+        if stype not in (2, 11) or not entsize:           # SHT_SYMTAB / SHT_DYNSYM
+            continue
+        str_off = sections[link][4]
+        for k in range(size // entsize):
+            st_name, _st_info, _other, shndx, value, st_size = struct.unpack_from("<IBBHQQ", data, off + k * entsize)
+            end = data.index(b"\0", str_off + st_name)
+            if data[str_off + st_name:end] == b"sa_meta" and 0 < shndx < shnum and st_size >= 24:
+                sec = sections[shndx]
+                vals = struct.unpack_from("<6i", data, sec[4] + (value - sec[3]))
+                return dict(zip(("n_states", "n_sub", "n_rem", "abi", "lanes", "ws_doubles"), vals))
+    raise ValueError("no sa_meta symbol in %s" % path)
 
 
 def toolchain_id() -> dict:
@@ -608,7 +658,8 @@ class NativeSolver:
                  atolB=1e-10, rtolQB=1e-10, atolQB=1e-10, mxstep=500, max_retries_fwd=5,
                  max_retries_bwd=50, traj_capacity=500_001, n_states: Optional[int] = None, sens: bool = False,
                  constraints=None, hermite: bool = False, arena_bytes: int = 0, compact: bool = False,
-                 guard: Optional[bool] = None, guard_sample: int = 64, guard_kinds=None, group: Optional[str] = None):
+                 guard: Optional[bool] = None, guard_sample: int = 64, guard_kinds=None, group: Optional[str] = None,
+                 band=None):
         """``guard`` (default: on, SA_GUARD=0 turns it off): the differential guard -- the conservative build of the
         same source is compiled next to the default one and a sample of the first batch of every kind of call (chosen
         from the batch's own statuses and counters, include/sunode_amd.h) runs through both on the device; any
@@ -618,6 +669,8 @@ class NativeSolver:
         kinds it never runs are not left pending, so the shadow handles go away once the used kind is verified."""
         self.L = load_library()
         build_kw = dict(sens=sens, constraints=constraints is not None, hermite=hermite, compact=compact, group=group)
+        if band is not None:        # (ml, mu): the band build; the guard's conservative partner gets the same defines
+            build_kw["band"] = tuple(int(w) for w in band)
         self.variant = kernel_variant(native_source, sens, constraints is not None, hermite, group=group)
         self._guard_open = False
         self._guard_safe = None

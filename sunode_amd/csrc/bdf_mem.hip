@@ -34,6 +34,9 @@
 #define SA_OUT_T SinkT
 #define SA_STORE(slot, value) out.template put<(slot)>(value)
 #define SA_STORE_DYN(slot, value) out.put_dyn(slot, value)
+#ifdef SA_BAND_ML   /* runs of structural zeros (codegen.ZERO_RUN_MIN) are the sink's business: a loop of stores, or nothing */
+#define SA_ZERO_RANGE(S0, N) out.zero_range((S0), (N))
+#endif
 #define SA_Y(i) y[(int64_t)(i) * sa_ystride]
 #define SA_LAM(i) lam[(int64_t)(i) * sa_ystride]
 /* the state views handed to the generated functions have the stride of their output sink */
@@ -71,8 +74,18 @@ constexpr int next_pow2_c(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 #define O_QUAD (O_LAM + NS)
 #define O_QOUT (O_QUAD + NQ)
 #define O_A (O_QOUT + NQ)
+#ifdef SA_BAND_ML   /* band build (linear_solver="band"): column j of the Newton matrix holds rows j-mu-ml .. j+ml (the upper
+                       ml rows take the fill-in of row exchanges), column j of the saved Jacobian rows j-mu .. j+ml.  The
+                       backward problem (Jacobian -J^T) has the widths swapped; the shared workspace holds the larger shape */
+#define BAND_WMAX (SA_BAND_ML > SA_BAND_MU ? SA_BAND_ML : SA_BAND_MU)
+#define BAND_LDS (SA_BAND_ML + SA_BAND_MU + 1)
+#define BAND_LDA_MAX (BAND_WMAX + BAND_LDS)
+#define O_SJ (O_A + BAND_LDA_MAX * NS)
+#define O_PIV (O_SJ + BAND_LDS * NS)
+#else
 #define O_SJ (O_A + NS * NS)
 #define O_PIV (O_SJ + NS * NS)
+#endif
 #define O_INVP (O_PIV + NS)
 #define O_HY (O_INVP + NS)
 #define O_F0 (O_HY + 6 * NS)
@@ -96,7 +109,33 @@ struct StrideSink {
     int64_t stride;
     template <int S> __device__ __forceinline__ void put(double x) const { p[(int64_t)S * stride] = x; }
     __device__ __forceinline__ void put_dyn(int slot, double x) const { p[(int64_t)slot * stride] = x; }
+#ifdef SA_BAND_ML
+    __device__ __forceinline__ void zero_range(int s0, int n) const { for (int z_ = 0; z_ < n; z_++) put_dyn(s0 + z_, 0.0); }
+#endif
 };
+#ifdef SA_BAND_ML
+static_assert(SA_BAND_ML >= 0 && SA_BAND_MU >= 0 && SA_BAND_ML < (NS > 0 ? NS : 1) && SA_BAND_MU < (NS > 0 ? NS : 1),
+              "band widths are clamped to n - 1 by the host");
+/* band sink for the Jacobian callbacks: slot S = j * NS + i of the column-major matrix goes to row i - j + ML + MU of
+   column j (2 * ML + MU + 1 rows per column); slots outside the band are structural zeros and are not stored */
+template <int ML, int MU>
+struct BandSink {
+    double *p;
+    int64_t stride;
+    static constexpr int LDA = 2 * ML + MU + 1;
+    template <int S> __device__ __forceinline__ void put(double x) const
+    {
+        constexpr int i = S % NS, j = S / NS;
+        if constexpr (i - j <= ML && j - i <= MU) p[(int64_t)(j * LDA + (i - j + ML + MU)) * stride] = x;
+    }
+    __device__ __forceinline__ void put_dyn(int slot, double x) const
+    {
+        const int i = slot % NS, j = slot / NS;
+        if (i - j <= ML && j - i <= MU) p[(int64_t)(j * LDA + (i - j + ML + MU)) * stride] = x;
+    }
+    __device__ __forceinline__ void zero_range(int, int) const {}      /* (cv_jac clears the band before the callback) */
+};
+#endif
 
 /* a vector of the instance: element r at p[r * S] (workspace: S = instance stride; caller arrays: S = 1) */
 struct Vec {
@@ -371,7 +410,16 @@ DEV int cv_fQ(Cm<BWD> &m, double t, const Vec &y, const Vec &out)
 template <bool BWD>
 DEV int cv_jac(Cm<BWD> &m, double t, const Vec &y)
 {
+#ifdef SA_BAND_ML
+    /* the band of the problem's Jacobian (backward: -J^T, widths swapped), cleared first: the callback stores in-band
+       slots only */
+    constexpr int ML = BWD ? SA_BAND_MU : SA_BAND_ML, MU = BWD ? SA_BAND_ML : SA_BAND_MU, LDA = 2 * ML + MU + 1;
+    for (int j = 0; j < NS; j++)
+        for (int r = ML; r < LDA; r++) W(m, O_A, j * LDA + r) = 0.0;
+    BandSink<ML, MU> sink{&W(m, O_A, 0), m.S};
+#else
     StrideSink sink{&W(m, O_A, 0), m.S};
+#endif
     if (BWD) return sa_adj_jac(t, m.ytmp.p, m.ps, m.pr, sink);
     return sa_jac(t, y.p, m.ps, m.pr, sink);
 }
@@ -399,6 +447,119 @@ DEV int cv_fS(Cm<BWD> &m, double t, const Vec &y)
 }
 #endif
 
+#ifdef SA_BAND_ML
+/* ---- band LU on the workspace matrix (linear_solver="band").  A partial-pivoting LU of a matrix whose entries outside
+   the band are exact zeros performs, on the entries inside it, the floating-point operations of the dense LU below in the
+   same order: the dense column search never prefers a zero below the band (v > best is strict), every update it skips
+   is fma(-a, 0, x) = x, and every element of a right-hand side receives the same updates in the same order.  Results
+   equal the dense build's (and the oracle's) bit for bit; only the sign of an exact zero is free. ---- */
+template <bool BWD>
+struct Band {
+    static constexpr int ML = BWD ? SA_BAND_MU : SA_BAND_ML, MU = BWD ? SA_BAND_ML : SA_BAND_MU;
+    static constexpr int SMU = ML + MU;          /* upper width of U: the fill-in of the row exchanges */
+    static constexpr int LDA = ML + SMU + 1, LDS = SMU + 1;
+};
+static_assert(Band<false>::LDA <= BAND_LDA_MAX && Band<true>::LDA <= BAND_LDA_MAX, "O_A holds both problems' band");
+/* entry (i, j), j - SMU <= i <= j + ML */
+#define BA(m, i, j) W(m, O_A, (j) * Band<BWD>::LDA + ((i) - (j) + Band<BWD>::SMU))
+
+template <bool BWD>
+DEV int band_getrf(Cm<BWD> &m)
+{
+    constexpr int ML = Band<BWD>::ML, SMU = Band<BWD>::SMU;
+    for (int k = 0; k < NS; k++) {
+        const int ilast = (k + ML < NS - 1) ? k + ML : NS - 1;       /* last row with an entry in column k */
+        const int jlast = (k + SMU < NS - 1) ? k + SMU : NS - 1;     /* last column with an entry in rows k .. ilast */
+        int l = k;
+        double best = fabs(BA(m, k, k));
+        for (int i = k + 1; i <= ilast; i++) {
+            double v = fabs(BA(m, i, k));
+            if (v > best) { best = v; l = i; }
+        }
+        W(m, O_PIV, k) = (double)l;
+        if (BA(m, l, k) == 0.0) return k + 1;
+        if (l != k) {       /* columns k .. jlast only: the multipliers of earlier columns stay where they are (band_getrs) */
+            for (int c = k; c <= jlast; c++) {
+                double tmp = BA(m, l, c);
+                BA(m, l, c) = BA(m, k, c);
+                BA(m, k, c) = tmp;
+            }
+        }
+        double mult = 1.0 / BA(m, k, k);
+        W(m, O_INVP, k) = mult;
+        for (int i = k + 1; i <= ilast; i++) BA(m, i, k) *= mult;
+        for (int j = k + 1; j <= jlast; j++) {
+            double a_kj = BA(m, k, j);
+            if (a_kj != 0.0) {
+                for (int i = k + 1; i <= ilast; i++) BA(m, i, j) = FMA(-a_kj, BA(m, i, k), BA(m, i, j));
+            }
+        }
+    }
+    return 0;
+}
+
+/* the interchanges are interleaved with the forward substitution: with multipliers that were not exchanged this is,
+   for every logical element, the dense "permute first, then substitute" */
+template <bool BWD, class B>
+DEV void band_getrs(const Cm<BWD> &m, B &b)
+{
+    constexpr int ML = Band<BWD>::ML, SMU = Band<BWD>::SMU;
+    for (int k = 0; k < NS - 1; k++) {
+        int pk = (int)W(m, O_PIV, k);
+        if (pk != k) { double tmp = b[k]; b[k] = b[pk]; b[pk] = tmp; }
+        const int ilast = (k + ML < NS - 1) ? k + ML : NS - 1;
+        double bk = b[k];
+        for (int i = k + 1; i <= ilast; i++) b[i] = FMA(-BA(m, i, k), bk, b[i]);
+    }
+    for (int k = NS - 1; k > 0; k--) {
+        double bk = b[k] * W(m, O_INVP, k);
+        b[k] = bk;
+        for (int i = (k > SMU ? k - SMU : 0); i < k; i++) b[i] = FMA(-BA(m, i, k), bk, b[i]);
+    }
+    if (NS > 0) b[0] = b[0] * W(m, O_INVP, 0);
+}
+template <bool BWD, class B>
+DEV void dense_getrs(const Cm<BWD> &m, B &b) { band_getrs(m, b); }       /* (bdf_core.h's name of the hook) */
+
+/* cvLsSetup: Jacobian (fresh or saved), I - gamma J, LU -- over band storage only */
+template <bool BWD>
+DEV int cv_lsetup(Cm<BWD> &m, int convfail)
+{
+    constexpr int ML = Band<BWD>::ML, MU = Band<BWD>::MU, LDA = Band<BWD>::LDA, LDS = Band<BWD>::LDS;
+    double dgamma = fabs((m.gamma / m.gammap) - 1.0);
+    int jbad = (m.nst == 0) || (m.nst > m.nstlj + MSBJ) ||
+               ((convfail == CV_FAIL_BAD_J) && (dgamma < CVLS_DGMAX)) ||
+               (convfail == CV_FAIL_OTHER);
+    int jret = 0;
+    if (!jbad) {
+        m.jcur = 0;
+        for (int j = 0; j < NS; j++)
+            for (int r = 0; r < LDS; r++) W(m, O_A, j * LDA + ML + r) = W(m, O_SJ, j * LDS + r);
+    } else {
+        m.nje++;
+        m.nstlj = m.nst;
+        m.jcur = 1;
+        jret = cv_jac(m, m.tn, m.y);
+        if (jret == 0) {
+            for (int j = 0; j < NS; j++)
+                for (int r = 0; r < LDS; r++) W(m, O_SJ, j * LDS + r) = W(m, O_A, j * LDA + ML + r);
+        }
+    }
+    if (jret < 0) return -1;
+    if (jret > 0) return 1;
+    const double c = -m.gamma;
+    for (int j = 0; j < NS; j++) {
+        for (int r = 0; r < ML; r++) W(m, O_A, j * LDA + r) = 0.0;          /* room for the fill-in */
+        for (int r = 0; r < LDS; r++) {
+            double &a = W(m, O_A, j * LDA + ML + r);
+            if (r == MU) a = FMA(c, a, 1.0);                                 /* (row j of column j) */
+            else a *= c;
+        }
+    }
+    int ier = band_getrf(m);
+    return ier > 0 ? 1 : 0;
+}
+#else
 /* ---- dense LU (denseGETRF / denseGETRS, column-major) on the workspace matrix ---- */
 #define AE(m, i, j) W(m, O_A, (j) * NS + (i))
 
@@ -483,6 +644,8 @@ DEV int cv_lsetup(Cm<BWD> &m, int convfail)
     int ier = dense_getrf(m);
     return ier > 0 ? 1 : 0;
 }
+
+#endif
 
 #include "bdf_core.h"
 static_assert(SA_TMPV_SLOTS == 20 && SA_TMPQ_SLOTS == 5, "O_TMP / O_TMPQ reserve 20 + 5 slots");

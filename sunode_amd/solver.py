@@ -7,7 +7,8 @@ handle (C ABI, include/sunode_amd.h) and integrate a whole batch per call; the s
 methods of the reference API are the B = 1 case of the same kernels.
 
 Scope: BDF with dense Newton/LU and analytic Jacobians in both
-directions, polynomial interpolation of the stored forward trajectory.  Options of the
+directions (``linear_solver="band"``: band storage and band LU where the memory-resident mapping runs, i.e. beyond
+128 states), polynomial interpolation of the stored forward trajectory.  Options of the
 reference outside that path raise ``NotImplementedError`` instead of silently doing
 something else.  There is no CPU fallback.
 """
@@ -114,6 +115,46 @@ class _OutputPool:
         return arr
 
 
+LINEAR_SOLVERS = ("dense", "dense_finitediff", "spgmr", "spgmr_finitediff", "band")
+
+
+def _resolve_linear_solver(problem, source, linear_solver, linear_solver_kwargs, stacklevel=3, **variant_kw):
+    """``band`` for the engine: (ml, mu) where ``linear_solver="band"`` is honoured -- the memory-resident mapping
+    (``_native.kernel_variant(...)[0] == "bdf_mem.hip"``: more than 128 states, ``SA_FORCE_GROUP=mem``, the sensitivity
+    builds that land there), which then stores and factors the band only (csrc/bdf_mem.hip) -- else None.
+
+    Everywhere else, and for the reference's other alternatives to ``"dense"`` (solver.py:326-358), the device
+    integrator has one way to solve the Newton systems: dense LU of I - gamma*J with the analytic Jacobian, in
+    registers / LDS.  The option is accepted with a RuntimeWarning so that reference code runs unchanged; results
+    agree to the integration tolerance.
+
+    Where the band is honoured a declaration narrower than the Jacobian's structure is an error: CVODES would drop
+    the entries outside it silently, here a wrong declaration must not produce wrong numbers.  A wider band is
+    allowed; widths are clamped to n - 1."""
+    if linear_solver not in LINEAR_SOLVERS:
+        raise ValueError(f"Unknown linear solver: {linear_solver}")
+    if linear_solver == "dense":
+        return None
+    if linear_solver == "band" and _native.kernel_variant(source, **variant_kw)[0] == "bdf_mem.hip":
+        kwargs = linear_solver_kwargs or {}
+        if "lower_bandwidth" not in kwargs or "upper_bandwidth" not in kwargs:
+            # (the reference's text, solver.py:350-353)
+            raise ValueError("Banded solver requires arguments lower_bandwidth and upper_bandwidth")
+        ml, mu = int(kwargs["lower_bandwidth"]), int(kwargs["upper_bandwidth"])
+        if ml < 0 or mu < 0:
+            raise ValueError("lower_bandwidth and upper_bandwidth must not be negative")
+        need = problem.jacobian_bandwidths()
+        if ml < need[0] or mu < need[1]:
+            raise ValueError("linear_solver='band': the declared (lower_bandwidth, upper_bandwidth) = %s is narrower "
+                             "than the Jacobian's structure, which needs %s" % ((ml, mu), need))
+        top = max(problem.n_states - 1, 0)
+        return min(ml, top), min(mu, top)
+    import warnings
+    warnings.warn(f"linear_solver={linear_solver!r}: the MI355X integrator always uses dense LU with the "
+                  "analytic Jacobian", RuntimeWarning, stacklevel=stacklevel)
+    return None
+
+
 def _is_device_tensor(x) -> bool:
     return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
 
@@ -130,6 +171,11 @@ class _EngineMixin:
     def _engine_kwargs(self) -> Dict[str, Any]:
         """Keyword arguments of one NativeSolver handle (without device / arena share)."""
         return self._native_kwargs()
+
+    def _band_kw(self) -> Dict[str, Any]:
+        """``band=(ml, mu)`` of the build where ``linear_solver="band"`` is honoured (``_resolve_linear_solver``)."""
+        band = getattr(self, "_band", None)
+        return {} if band is None else {"band": tuple(band)}
 
     # -- devices (SURVEY.md section 8e: the batch shards by instance, no exchange step) ------------
     # ``devices=[0, 1, ..., 7]``: ONE Python process drives several GPUs -- the reference's call pattern is one solver
@@ -468,15 +514,8 @@ class Solver(_EngineMixin):
             if solver == "ADAMS":
                 raise NotImplementedError("only the BDF method is implemented on the device")
             raise ValueError(f"Unknown solver {solver}.")
-        if linear_solver not in ("dense", "dense_finitediff", "spgmr", "spgmr_finitediff", "band"):
+        if linear_solver not in LINEAR_SOLVERS:
             raise ValueError(f"Unknown linear solver: {linear_solver}")
-        if linear_solver != "dense":
-            # The reference offers these as alternative ways to solve the same Newton systems (solver.py:326-358).
-            # The device integrator has one: dense LU of I - gamma*J with the analytic Jacobian.  The option is
-            # accepted so that reference code runs unchanged; results agree to the integration tolerance.
-            import warnings
-            warnings.warn(f"linear_solver={linear_solver!r}: the MI355X integrator always uses dense LU with the "
-                          "analytic Jacobian", RuntimeWarning, stacklevel=2)
         if constraints is not None:
             constraints = np.broadcast_to(np.asarray(constraints, dtype=np.float64), (problem.n_states,)).copy()
             if not np.isin(constraints, (0.0, 1.0, -1.0, 2.0, -2.0)).all():
@@ -500,15 +539,20 @@ class Solver(_EngineMixin):
         self._batch_mapping = batch_mapping if sens_mode is None else "fixed"
         self._init_devices(device, devices, interleaved)
         self._set_tolerances(abstol, reltol)
+        # ("band" is honoured in the memory-resident mapping and answered with a RuntimeWarning elsewhere)
+        self._band = _resolve_linear_solver(problem, problem.native_source(), linear_solver, linear_solver_kwargs,
+                                            sens=self._compute_sens, constraints=constraints is not None)
         self._state_names = ["_problem", "_user_data", "_constraints", "_abstol", "_reltol", "_batch_mapping",
                              "_linear_solver_kind", "_linear_solver_kwargs", "_sens_mode", "_scaling_factors",
-                             "_mxsteps", "_device", "_devices", "_interleaved", "_reuse_outputs", "_state_names"]
+                             "_mxsteps", "_device", "_devices", "_interleaved", "_reuse_outputs", "_band",
+                             "_state_names"]
         self._init_native()
 
     def _init_native(self):
         self._source = self._problem.native_source()
         # compile at construction like the reference JITs; sensitivity solves use their own build
-        _native.build_code_object(self._source, sens=self._compute_sens, constraints=self._constraints is not None)
+        _native.build_code_object(self._source, sens=self._compute_sens, constraints=self._constraints is not None,
+                                  **self._band_kw())
         self._native = None
         self._natives = None
         self._native_sets = {}
@@ -517,7 +561,7 @@ class Solver(_EngineMixin):
 
     def _engine_kwargs(self):
         return dict(self._native_kwargs(), sens=self._compute_sens, constraints=self._constraints,
-                    guard_kinds=("sens",) if self._compute_sens else ("plain",))
+                    guard_kinds=("sens",) if self._compute_sens else ("plain",), **self._band_kw())
 
     def __getstate__(self):
         return {name: self.__dict__[name] for name in self._state_names}
@@ -526,6 +570,7 @@ class Solver(_EngineMixin):
         self.__dict__.update(state)
         self._reuse_outputs = state.get("_reuse_outputs", False)
         self._batch_mapping = state.get("_batch_mapping", "auto" if self._sens_mode is None else "fixed")
+        self._band = state.get("_band")
         self._outputs = _OutputPool() if self._reuse_outputs else None
         self._compute_sens = self._sens_mode is not None
         self._set_tolerances(self._abstol, self._reltol)
@@ -654,6 +699,9 @@ class AdjointSolver(_EngineMixin):
     backward kernel rebuild the table when its index moves: 5x less arena and HBM traffic (one-lane-per-instance
     kernel, polynomial interpolation; ignored elsewhere); results identical.  Default (None): on from three states
     (Robertson B = 262 144: 73 -> 14 GB, 2.37 -> 2.79 M solves/s; Lotka-Volterra, n = 2, is 4 % faster without).
+    ``linear_solver="band"`` with ``linear_solver_kwargs={"lower_bandwidth": ml, "upper_bandwidth": mu}`` as ``Solver``
+    takes them: band storage and band LU of both problems' Newton matrices where the memory-resident mapping runs (more
+    than 128 states; ``_resolve_linear_solver``), results unchanged bit for bit; a RuntimeWarning and the dense LU elsewhere.
     """
 
     def __init__(self, problem, *, abstol=1e-10, reltol=1e-10, checkpoint_n=500_000, interpolation="polynomial",
@@ -661,9 +709,12 @@ class AdjointSolver(_EngineMixin):
                  backward_reltol=1e-10, quad_abstol=1e-10, quad_reltol=1e-10, mxsteps: int = 500,
                  max_steps: Optional[int] = None, arena_gib: Optional[float] = None, device: int = 0,
                  compact_trajectory: Optional[bool] = None, devices=None, interleaved: bool = False,
-                 reuse_outputs: bool = False, batch_mapping: str = "auto"):
+                 reuse_outputs: bool = False, batch_mapping: str = "auto", linear_solver="dense",
+                 linear_solver_kwargs=None):
         if batch_mapping not in ("auto", "fixed"):
             raise ValueError('batch_mapping must be "auto" or "fixed"')
+        if linear_solver not in LINEAR_SOLVERS:
+            raise ValueError(f"Unknown linear solver: {linear_solver}")
         if solver not in ("BDF", "ADAMS"):
             raise ValueError(f"Unknown solver {solver}.")
         if adjoint_solver not in ("BDF", "ADAMS"):
@@ -689,13 +740,19 @@ class AdjointSolver(_EngineMixin):
         self._reuse_outputs = bool(reuse_outputs)
         self._init_devices(device, devices, interleaved)
         self._source = problem.native_source()
+        # linear_solver / linear_solver_kwargs as ``Solver`` takes them (the reference's AdjointSolver has neither): the
+        # band is honoured in the memory-resident mapping, for the forward and the backward problem (-J^T: widths swapped)
+        self._linear_solver_kind = linear_solver
+        self._linear_solver_kwargs = linear_solver_kwargs or {}
+        self._band = _resolve_linear_solver(problem, self._source, linear_solver, linear_solver_kwargs,
+                                            constraints=constraints is not None, hermite=self._hermite)
         # (bdf_kernels.hip and bdf_wave.hip carry the compact-record option)
         if compact_trajectory is None:        # measured (profiles/r03_compact_trajectory.txt): pays from three states on
             compact_trajectory = _native.default_compact_trajectory(self._source, self._hermite)
         self._compact = bool(compact_trajectory) and not self._hermite and \
             _native.kernel_variant(self._source, hermite=self._hermite)[0] in ("bdf_kernels.hip", "bdf_wave.hip")
         _native.build_code_object(self._source, constraints=self._constraints is not None, hermite=self._hermite,
-                                  compact=self._compact)
+                                  compact=self._compact, **self._band_kw())
         self._native = None
         self._last_forward = None
         # small batches run with more lanes per instance (measured: _native.small_batch_group); the code object of such a
@@ -704,7 +761,7 @@ class AdjointSolver(_EngineMixin):
 
     def _engine_kwargs(self):
         return dict(self._native_kwargs(), constraints=self._constraints, hermite=self._hermite,
-                    compact=self._compact, guard_kinds=("adjoint",))
+                    compact=self._compact, guard_kinds=("adjoint",), **self._band_kw())
 
     def _set_tolerances(self, atol=None, rtol=None):
         atol, rtol = np.array(atol, dtype=float), np.array(rtol, dtype=float)

@@ -313,6 +313,16 @@ class SympyProblem:
     def n_remainder(self) -> int:
         return self.params_subset.n_items - self.params_subset.n_subset
 
+    def jacobian_bandwidths(self) -> Tuple[int, int]:
+        """(ml, mu): the largest i - j and j - i over the structurally non-zero entries (i, j) of the Jacobian
+        d(dydt_i)/d(y_j) -- the ``lower_bandwidth`` / ``upper_bandwidth`` that ``linear_solver="band"`` needs at
+        least (reference solver.py:349-356).  (0, 0) for a diagonal or empty Jacobian."""
+        ml = mu = 0
+        for (i, j), entry in np.ndenumerate(self._sym_dydt_jac):
+            if entry != 0:
+                ml, mu = max(ml, i - j), max(mu, j - i)
+        return ml, mu
+
     # ------------------------------------------------------------------
     def _make_dydt(self) -> sym.Matrix:
         """Call the user's rhs and flatten its nested result in state order

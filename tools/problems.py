@@ -249,6 +249,54 @@ def pivoting(t, y, p):
                   -x[5] + x[0]]}
 
 
+def pivoting_band(t, y, p):
+    """``pivoting`` with its last equation fed by x[4] instead of x[0]: the same row exchanges in a tridiagonal
+    Jacobian, (ml, mu) = (1, 1) -- the band LU's pivoting fixture."""
+    x = y.x
+    return {"x": [-p.k[0] * x[0] + 1.0,
+                  p.w[0] * x[2], -p.w[0] * x[1],
+                  p.w[1] * x[4] - p.k[1] * x[3], -p.w[1] * x[3],
+                  -x[5] + x[4]]}
+
+
+def make_brusselator1d(N: int):
+    """The Brusselator with diffusion on N cells of the unit interval, zero flux at both ends (method of lines):
+    u' = A + u^2 v - (B + 1) u + D N^2 lap(u), v' = B u - u^2 v + D N^2 lap(v).  The states are interleaved,
+    x[2i] = u_i, x[2i + 1] = v_i, so the Jacobian has (ml, mu) = (2, 2): nonlinear, stiff, the textbook band example."""
+    def rhs(t, y, p):
+        x = y.x
+        u, v = [x[2 * i] for i in range(N)], [x[2 * i + 1] for i in range(N)]
+        c = p.D * (N * N)
+
+        def lap(w, i):
+            return (w[i - 1] - w[i] if i > 0 else 0) + (w[i + 1] - w[i] if i < N - 1 else 0)
+        out = []
+        for i in range(N):
+            out.append(p.A + u[i] ** 2 * v[i] - (p.B + 1) * u[i] + c * lap(u, i))
+            out.append(p.B * u[i] - u[i] ** 2 * v[i] + c * lap(v, i))
+        return {"x": out}
+    return rhs
+
+
+def brusselator1d(N: int):
+    return dict(params={"A": (), "B": (), "D": ()}, states={"x": (2 * N,)}, rhs=make_brusselator1d(N),
+                derivative_params=[("A",), ("B",)])
+
+
+def brusselator1d_batch(B: int, N: int, seed: int = SEED, idx=None):
+    """Draws for ``brusselator1d(N)``: A, B around (1, 3) (the limit-cycle regime), D = 0.02 shared, a smooth initial
+    profile, per-instance cotangents; 5 output times on [0, 2]."""
+    z = np.stack([std_normal(seed, 1400 + s, B, idx) for s in range(2)], axis=1)
+    ps = np.array([1.0, 3.0]) * np.exp(0.1 * z)
+    xc = (np.arange(N) + 0.5) / N
+    y0 = np.empty((len(z), 2 * N))
+    y0[:, 0::2] = 1.0 + 0.5 * np.sin(2 * np.pi * xc)
+    y0[:, 1::2] = 3.0
+    tvals = np.array([0.0, 0.25, 0.5, 1.0, 2.0])
+    return dict(ps=ps, pr=np.array([0.02]), y0=y0, tvals=tvals, t0=0.0,
+                grads=_cotangents(len(z), len(tvals), 2 * N, idx), rtol=1e-8, atol=1e-8)
+
+
 PROBLEMS = {
     "lv": dict(
         params={"alpha": (), "beta": (), "gamma": (), "delta": ()},
@@ -468,6 +516,12 @@ EXTRA_PROBLEMS = {
         params={"k": (2,), "w": (2,)},
         states={"x": (6,)},
         rhs=pivoting,
+        derivative_params=[("k",)],
+    ),
+    "pivoting_band": dict(
+        params={"k": (2,), "w": (2,)},
+        states={"x": (6,)},
+        rhs=pivoting_band,
         derivative_params=[("k",)],
     ),
 }
