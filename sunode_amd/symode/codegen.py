@@ -25,8 +25,10 @@ transcendental right-hand sides.  The implementations live in the function block
 ``MATH_BLOCKS`` below, one ``csrc/sa_math*.h`` header each; the table names every
 function and the sympy class printed as it.  A block is embedded into a generated
 header in table order and only when a callback calls one of its functions (the first
-block whenever any is), so that the headers of models without them keep their text
-(and with it their cache keys and code objects).  ``polygamma(n, .)`` with n >= 2 and
+block whenever any is) or a block that is embedded ``requires`` it, so that the headers
+of models without them keep their text (and with it their cache keys and code objects).
+``lowergamma / uppergamma`` with a shape that depends on a state or on a differentiated
+parameter raise: the derivative with respect to the shape is a Meijer G function.  ``polygamma(n, .)`` with n >= 2 and
 Bessel functions of a non-integer, symbolic or larger order than ``SAM_BESSEL_NMAX``
 have no implementation and raise.  Functions outside the table (``LIBM_ONLY``: cbrt,
 hypot, exp2, log2, log10) still compile, through libm / ocml, without the
@@ -353,6 +355,13 @@ class HipExprPrinter(C99CodePrinter):
     def _print_factorial(self, expr):
         return "sa_tgamma(%s)" % self._print(expr.args[0] + 1)
 
+    def _print_meijerg(self, expr):
+        # what sympy gives d lowergamma(a, x) / da and d uppergamma(a, x) / da (generate_problem_source names the
+        # function before a printer gets here; a Meijer G function written into a model directly ends here too)
+        raise NotImplementedError(
+            "meijerg has no implementation.  It is the derivative of lowergamma(a, x) / uppergamma(a, x) with respect to "
+            "the shape a: the shape must be a literal or a non-differentiated parameter (csrc/sa_math_prob.h)")
+
     # Bessel functions of integer order: csrc/sa_math_bessel.h.  The order is printed as an
     # integer literal; sympy folds a negative integer order into a positive one itself, what is left of one goes
     # through J_-n = (-1)^n J_n, Y_-n = (-1)^n Y_n, I_-n = I_n, K_-n = K_n
@@ -430,6 +439,7 @@ class MathBlock(NamedTuple):
     header: str                             # file under csrc/
     calls: Tuple[str, ...]                  # the functions sa_<call> of the header that generated text may call
     printers: Tuple[Tuple[str, str], ...]   # (sympy function, call): printed as the plain call sa_<call>(args)
+    requires: Tuple[str, ...] = ()          # the blocks (besides the first) whose functions the header calls: embedded with it
 
     def called_in(self, text: str) -> bool:
         return re.search(r"\bsa_(%s)\(" % "|".join(self.calls), text) is not None
@@ -454,6 +464,11 @@ MATH_BLOCKS = (
     MathBlock("gamma", "sa_math_gamma.h", ("lgamma", "tgamma", "digamma", "trigamma"),
               (("gamma", "tgamma"), ("loggamma", "lgamma"), ("digamma", "digamma"), ("trigamma", "trigamma"))),
     MathBlock("bessel", "sa_math_bessel.h", ("bessel_j", "bessel_y", "bessel_i", "bessel_k"), ()),
+    # lowergamma(a, x) / uppergamma(a, x): the derivative with respect to x is x^(a - 1) e^-x (sa_pow, sa_exp); the one
+    # with respect to the shape a is a Meijer G function and raises (incomplete_gamma_shape_derivatives)
+    MathBlock("prob", "sa_math_prob.h", ("erfinv", "erfcinv", "igamma_lower", "igamma_upper"),
+              (("erfinv", "erfinv"), ("erfcinv", "erfcinv"), ("lowergamma", "igamma_lower"), ("uppergamma", "igamma_upper")),
+              requires=("inv", "gamma")),
 )
 
 for _block in MATH_BLOCKS:
@@ -1060,6 +1075,14 @@ def generate_problem_source(
     n = n_states
     matvec = matvec or {}
     matfill = matfill or {}
+    shaped = incomplete_gamma_shape_derivatives(
+        np.asarray(dydt, dtype=object).ravel(),
+        [e for a in (jac, quad, dydp_t) if a is not None for e in np.asarray(a, dtype=object).ravel()])
+    if shaped:
+        raise NotImplementedError(
+            "%s: the derivative of an incomplete gamma function with respect to its shape is a Meijer G function, which has "
+            "no implementation -- the shape (first argument) must be a literal or a non-differentiated parameter, not a "
+            "state or a differentiated parameter (csrc/sa_math_prob.h)" % ", ".join(shaped))
 
     def mv(tag):
         return dict(matvec[tag], tag=tag) if tag in matvec else None
@@ -1102,7 +1125,9 @@ def generate_problem_source(
     ]
     used = [block for block in MATH_BLOCKS if any(block.called_in(part) for part in parts if part)]
     if used:                    # in table order; the first block whenever any is: the others build on it
-        parts[6] = "\n".join(math_block_text(block.name) for block in MATH_BLOCKS if block in used or block is MATH_BLOCKS[0])
+        needed = {name for block in used for name in block.requires}
+        parts[6] = "\n".join(math_block_text(block.name) for block in MATH_BLOCKS
+                             if block in used or block.name in needed or block is MATH_BLOCKS[0])
     else:
         parts[6] = "/* (no transcendental function: csrc/sa_math.h not embedded) */"
     if any(_MINMAX_CALL.search(part) for part in parts[7:] if part):
@@ -1183,6 +1208,25 @@ def delta_functions(rhs, derivatives) -> List[str]:
             if f.args[0] in args:
                 found.add(str(f))
     return sorted(found) or sorted(str(d) for d in deltas)
+
+
+def incomplete_gamma_shape_derivatives(rhs, derivatives) -> List[str]:
+    """The ``lowergamma(a, x)`` / ``uppergamma(a, x)`` terms of a right-hand side (``rhs``: its expressions) that were
+    differentiated with respect to their shape ``a``: sympy writes that derivative with ``meijerg([], [1, 1], [0, 0, a],
+    [], x)``, found in ``derivatives`` (Jacobian, quadrature, df/dp).  There is no implementation of it, so such a model is
+    refused (generate_problem_source); a shape that is a literal or a remaining parameter is never differentiated."""
+    shapes = set()
+    for e in derivatives:
+        for g in sym.sympify(e).atoms(sym.meijerg):
+            shapes.add(tuple(g.bm)[-1] if len(g.bm) else None)
+    if not shapes:
+        return []
+    found = set()
+    for e in rhs:
+        for f in sym.sympify(e).atoms(sym.lowergamma, sym.uppergamma):
+            if f.args[0] in shapes:
+                found.add(str(f))
+    return sorted(found) or ["lowergamma / uppergamma"]
 
 
 def source_hash(text: str, extra: Iterable[str] = ()) -> str:

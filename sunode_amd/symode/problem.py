@@ -630,7 +630,7 @@ class SympyProblem:
         pieces = [flat]
         if self._hoisted:
             if self._hoist_fn is None:
-                self._hoist_fn = sym.lambdify([list(self._sym_fixed_paramsvec)], self._hoisted,
+                self._hoist_fn = sym.lambdify([list(self._sym_fixed_paramsvec)], [host_form(e) for e in self._hoisted],
                                               modules=[_HOST_HELPERS, "numpy"], cse=True)
             with np.errstate(all="ignore"):
                 extra = np.array([np.asarray(self._hoist_fn(list(row)), dtype=np.float64) for row in flat])
@@ -686,7 +686,7 @@ class SympyProblem:
             if with_lamda:
                 args.append(list(self._sym_lamda))
             args += [list(self._sym_deriv_paramsvec), list(self._sym_fixed_paramsvec)]
-            flat = [sym.sympify(e) for e in np.asarray(expr, dtype=object).ravel()]
+            flat = [host_form(e) for e in np.asarray(expr, dtype=object).ravel()]
             fn = sym.lambdify(args, flat, modules=[_HOST_HELPERS, "numpy"], cse=True)
             self._host_funcs[key] = (fn, np.asarray(expr, dtype=object).shape)
         return self._host_funcs[key]
@@ -730,6 +730,16 @@ class SympyProblem:
         def jac_dense(out, t, y, yB, fyB, user_data):
             return self._eval_host("adjjac", -self._sym_dydt_jac.T, False, out, t, y, None, user_data)
         return jac_dense
+
+
+def host_form(expr):
+    """``expr`` as ``sympy.lambdify(..., modules=[HOST_FUNCTIONS, "numpy"])`` can print it: sympy's numpy printer refuses
+    ``lowergamma / uppergamma`` outright (before it looks a name up in the modules), so they are handed over as plain
+    function calls of those names -- ``_HOST_HELPERS`` defines them.  Every other expression is returned as it is."""
+    expr = sym.sympify(expr)
+    if not expr.has(sym.lowergamma, sym.uppergamma):
+        return expr
+    return expr.replace(sym.lowergamma, sym.Function("lowergamma")).replace(sym.uppergamma, sym.Function("uppergamma"))
 
 
 def _logaddexp(a, b):
@@ -780,6 +790,26 @@ def _factorial(x):
     return special.gamma(np.asarray(x, dtype=float) + 1.0)
 
 
+def _erfinv(x):
+    from scipy import special
+    return special.erfinv(x)
+
+
+def _erfcinv(x):
+    from scipy import special
+    return special.erfcinv(x)
+
+
+def _lowergamma(a, x):
+    from scipy import special           # (scipy's are the regularised functions P and Q)
+    return special.gammainc(a, x) * special.gamma(a)
+
+
+def _uppergamma(a, x):
+    from scipy import special
+    return special.gammaincc(a, x) * special.gamma(a)
+
+
 def _bessel(kind):
     def fn(n, x):
         from scipy import special
@@ -794,6 +824,10 @@ _HOST_HELPERS = {
     "besselk": _bessel("kv"),
     "erf": _erf,
     "erfc": _erfc,
+    "erfinv": _erfinv,
+    "erfcinv": _erfcinv,
+    "lowergamma": _lowergamma,
+    "uppergamma": _uppergamma,
     "gamma": _gamma,
     "loggamma": _loggamma,
     "polygamma": _polygamma,

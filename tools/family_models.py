@@ -34,6 +34,8 @@ FAMILY_MODELS = (
     FamilyModel("probit_gate", P.probit_gate_batch, 16, conservative=True, sens=True, mappings=("wave4", "wave", "mem")),
     FamilyModel("gamma_delay", P.gamma_delay_batch, 16, conservative=True, sens=True, mappings=("wave4", "wave", "mem")),
     FamilyModel("bessel_ring", P.bessel_ring_batch, 16, conservative=True, sens=True, mappings=("wave4", "wave", "mem")),
+    # erfinv / erfcinv / incomplete gamma functions (tests/test_gpu_prob.py)
+    FamilyModel("quantile_delay", P.quantile_delay_batch, 16, conservative=True, sens=True, mappings=("wave4", "wave", "mem")),
     # non-smooth right-hand sides (tests/test_gpu_nonsmooth.py)
     FamilyModel("kinked", P.kinked_batch, 8, sens=True, hermite=True, mappings=("wave4", "wave8", "wave", "mem")),
     _threshold_sir(4), _threshold_sir(8), _threshold_sir(16),

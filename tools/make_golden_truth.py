@@ -15,7 +15,7 @@ Independent oracles for the integrator half:
 
 Usage: python tools/make_golden_truth.py   (a few minutes; outputs are committed)
        python tools/make_golden_truth.py --times    (only truth_times_<name>.npz: see ``times_truth``)
-       python tools/make_golden_truth.py --transcendental | --inverse-erf | --gamma | --bessel
+       python tools/make_golden_truth.py --transcendental | --inverse-erf | --gamma | --bessel | --prob
                                                     (only the fixtures of that family: see ``FAMILY_FLAGS``, ``family_truth``)
        python tools/make_golden_truth.py --nonsmooth    (only truth_kinked.npz, truth_threshold_sir8.npz: see ``nonsmooth_truth``)
 """
@@ -33,7 +33,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 from sunode_amd import SympyProblem  # noqa: E402
-from sunode_amd.symode.problem import HOST_FUNCTIONS  # noqa: E402
+from sunode_amd.symode.problem import HOST_FUNCTIONS, host_form  # noqa: E402
 from tools.family_models import FAMILY  # noqa: E402
 from tools.problems import (EXTRA_PROBLEMS, PROBLEMS, _cotangents, forcing_batch, lv_batch, misc_batch,  # noqa: E402
                             robertson_batch, seir_batch)
@@ -52,9 +52,9 @@ def augmented_rhs(prob):
     y = list(prob._sym_statevec)
     ps = list(prob._sym_deriv_paramsvec)
     pr = list(prob._sym_fixed_paramsvec)
-    f = sym.lambdify([prob._sym_time, y, ps, pr], list(prob._sym_dydt), modules=[HOST_FUNCTIONS, "numpy"], cse=True)
-    J = sym.lambdify([prob._sym_time, y, ps, pr], sym.Matrix(prob._sym_dydt_jac), modules=[HOST_FUNCTIONS, "numpy"], cse=True)
-    P = sym.lambdify([prob._sym_time, y, ps, pr], sym.Matrix(prob._sym_dydp), modules=[HOST_FUNCTIONS, "numpy"], cse=True) if p else None
+    f = sym.lambdify([prob._sym_time, y, ps, pr], [host_form(e) for e in prob._sym_dydt], modules=[HOST_FUNCTIONS, "numpy"], cse=True)
+    J = sym.lambdify([prob._sym_time, y, ps, pr], sym.Matrix(prob._sym_dydt_jac).applyfunc(host_form), modules=[HOST_FUNCTIONS, "numpy"], cse=True)
+    P = sym.lambdify([prob._sym_time, y, ps, pr], sym.Matrix(prob._sym_dydp).applyfunc(host_form), modules=[HOST_FUNCTIONS, "numpy"], cse=True) if p else None
 
     def rhs(t, z, psv, prv):
         yv = z[:n]
@@ -124,7 +124,7 @@ def dvode_run(f, jac, y0, tvals, rtol, atol, args):
 def family_truth(name):
     """truth_<name>.npz of an integrated model of a smooth function family (tools/family_models.py: its batch and number
     of draws, per-instance cotangents).  Nothing of csrc/sa_math*.h is on this side: the host functions are numpy's and
-    scipy.special's (erf / erfc; gammaln / gamma / digamma / polygamma; jv / yv / iv / kv), and the B-spline of ``forcing``
+    scipy.special's (erf / erfc; gammaln / gamma / digamma / polygamma; jv / yv / iv / kv; erfinv / erfcinv / gammainc / gammaincc), and the B-spline of ``forcing``
     is evaluated by the Cox-de Boor recursion, NOT by the polynomial pieces the generated code shares with the
     reference."""
     prob = make(name)
@@ -136,7 +136,7 @@ def family_truth(name):
 
 #: command-line flag -> the models whose truth ``family_truth`` writes
 FAMILY_FLAGS = {"--transcendental": ("forcing", "logistic_switch", "misc"), "--inverse-erf": ("probit_gate",),
-                "--gamma": ("gamma_delay",), "--bessel": ("bessel_ring",)}
+                "--gamma": ("gamma_delay",), "--bessel": ("bessel_ring",), "--prob": ("quantile_delay",)}
 
 
 #: what the two DOP853 runs of ``nonsmooth_truth`` (rtol 1e-13 and 1e-11) must agree to, in the tests' own error

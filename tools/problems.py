@@ -228,6 +228,36 @@ def bessel_ring(t, y, p):
     }
 
 
+def mathfn_g(t, y, p):
+    """One or two functions of csrc/sa_math_prob.h per output -- erfinv / erfcinv / lowergamma / uppergamma -- with a
+    product or a quotient of a state and a differentiated parameter as the argument.  The derivatives bring
+    exp(erfinv^2), exp(erfcinv^2) and x^(a - 1) e^-x (sa_pow, sa_exp) into the Jacobian, the adjoint and the quadrature.
+    The shape of an incomplete gamma function may be neither a state nor a differentiated parameter (its derivative is
+    a Meijer G function): outputs 2 and 3 take the TIME as a run-time shape, output 4 a literal."""
+    import sympy as sym
+    x, a = y.x, p.a
+    return {"x": [sym.erfinv(a[0] * x[0]), sym.erfcinv(x[1] / a[1]), sym.lowergamma(t, a[2] * x[2]),
+                  sym.uppergamma(t, x[3] / a[3]), sym.lowergamma(sym.Rational(7, 3), a[4] * x[4]) + sym.erfcinv(x[4])]}
+
+
+def quantile_delay(t, y, p):
+    """A PyMC-shaped model on the inverse error function and the incomplete gamma functions: the activity x in (0, 1)
+    is switched on through a gamma-distributed delay written as its CDF, lowergamma(a, t / theta) / gamma(a) (scale theta
+    inferred, shape a a fixed parameter), and saturates at r / (r + m); the response z follows the quantile (probit)
+    transform of the activity, s erfinv(b (2 x - 1)) -- a state inside erfinv, so the Jacobian and the adjoint carry
+    exp(erfinv^2) --, against a linear loss; the read-out c accumulates the survival function
+    uppergamma(a, k (x + z^2)) / gamma(a).  b (2 x - 1) stays inside (-0.9, 0.9) for the default draws; b = 6 puts it
+    beyond -1 at the initial state: erfinv is NaN there, a per-instance solver failure at the first call."""
+    import sympy as sym
+    x, z, c = y.x, y.z, y.c
+    cdf = sym.lowergamma(p.a, t / p.theta) / sym.gamma(p.a)
+    return {
+        "x": p.r * cdf * (1 - x) - p.m * x,
+        "z": p.s * sym.erfinv(p.b * (2 * x - 1)) - p.d * z,
+        "c": p.q * sym.uppergamma(p.a, p.k * (x + z * z)) / sym.gamma(p.a) - c / 5,
+    }
+
+
 def huge_pivots(t, y, p):
     """Decay rates of 1e200 on components that are exactly zero: the Newton matrix I - gamma*J has diagonal entries
     around 1e200 (beyond 2^500) while the steps stay of order 1 -- the pivots' reciprocals leave the range in which the
@@ -480,6 +510,13 @@ EXTRA_PROBLEMS = {
         rhs=bessel_ring,
         derivative_params=[("b",), ("w",), ("g",), ("A",), ("kappa",)],
     ),
+    "mathfn_g": dict(params={"a": (5,)}, states={"x": (5,)}, rhs=mathfn_g, derivative_params=[("a",)]),
+    "quantile_delay": dict(
+        params={"theta": (), "b": (), "k": (), "r": (), "s": (), "a": (), "m": (), "d": (), "q": ()},
+        states={"x": (), "z": (), "c": ()},
+        rhs=quantile_delay,
+        derivative_params=[("theta",), ("b",), ("k",), ("r",), ("s",)],
+    ),
     "sir2": dict(
         params={"beta": (2,), "C": (2, 2), "gamma": (), "pop": (2,)},
         states={"S": (2,), "I": (2,)},
@@ -669,6 +706,56 @@ def gamma_delay_batch(B: int, seed: int = SEED, idx=None):
     tvals = np.linspace(0, 8, 9)
     return dict(ps=ps, pr=np.array([0.5, 0.6, 0.05, 0.4]), y0=y0, tvals=tvals, t0=0.0,
                 grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
+
+
+def quantile_delay_batch(B: int, seed: int = SEED, idx=None):
+    """Draws for ``quantile_delay``: subset (theta, b, k, r, s), remainder (a, m, d, q).  Over t in [0, 8] the argument
+    t / theta of the delay runs from 0 to about 8 at the shape a = 2.5: through the lower series (below a - 1/3) into the
+    continued fraction; x rises from about 0.3 towards r / (r + m) = 0.83, so b (2 x - 1) runs from -0.36 to 0.6."""
+    z = np.stack([std_normal(seed, 1360 + k, B, idx) for k in range(5)], axis=1)
+    ps = np.array([1.0, 0.9, 1.2, 1.5, 0.8]) * np.exp(0.1 * z)
+    zy = np.stack([std_normal(seed, 1370 + s, B, idx) for s in range(2)], axis=1)
+    y0 = np.concatenate([np.array([0.3, 0.2]) * np.exp(0.1 * zy), np.zeros((len(z), 1))], axis=1)
+    tvals = np.linspace(0, 8, 9)
+    return dict(ps=ps, pr=np.array([2.5, 0.3, 0.6, 0.7]), y0=y0, tvals=tvals, t0=0.0,
+                grads=_cotangents(len(z), len(tvals), 3, idx), rtol=1e-8, atol=1e-8)
+
+
+def mathfn_g_points(N: int):
+    """(y, par, lam, t) for the callbacks of ``mathfn_g``: about three quarters of the points lie inside every function's
+    domain -- in every piece, on every boundary constant of csrc/sa_math_prob.h and at the edges (one point in 16 has
+    all parameters 1, so that its arguments are the drawn values exactly) --, the rest outside: |u| > 1 for erfinv,
+    u < 0 or u > 2 for erfcinv, a shape above SAM_IGAMMA_AMAX = 32 or a negative argument for the incomplete gamma
+    functions.  The time is the run-time shape of outputs 2 and 3."""
+    rng = np.random.RandomState(13)
+    pick = lambda *options: np.choose(rng.randint(0, len(options), N), options)     # noqa: E731
+    sign = lambda: rng.choice([-1.0, 1.0], N)                                        # noqa: E731
+    exact = np.arange(N) % 16 == 3
+    par = np.where(exact[:, None], 1.0, rng.uniform(0.5, 2.0, (N, 5)))
+    outside = rng.uniform(0, 1, (N, 5)) < 0.12
+    # erfinv: central piece, tail, next to +-1, tiny, the boundary 3/4 and the edge 1
+    u0 = sign() * pick(rng.uniform(0, 0.75, N), rng.uniform(0.75, 1.0, N), 1.0 - 10.0 ** rng.uniform(-16, -1, N),
+                       10.0 ** rng.uniform(-300, -1, N), np.full(N, 0.75), np.where(exact, 1.0, 0.7500000000000001))
+    u0 = np.where(outside[:, 0], sign() * rng.uniform(1.0, 3.0, N), u0)
+    # erfcinv: both tails, the centre, the boundaries 1/4 and 7/4, the edges 0 and 2
+    u1 = pick(10.0 ** rng.uniform(-300, np.log10(0.25), N), rng.uniform(0.25, 1.75, N), 2.0 - 10.0 ** rng.uniform(-16, np.log10(0.25), N),
+              np.full(N, 0.25), np.full(N, 1.75), np.where(exact, rng.choice([0.0, 2.0], N), 1.0))
+    u1 = np.where(outside[:, 1], rng.choice([-1.0, 1.0], N) * rng.uniform(2.0, 4.0, N), u1)
+    # the shape: (0, 32] on a linear and on a logarithmic scale, the edge 32; beyond it for one point in eight
+    t = pick(rng.uniform(0, 32, N), 10.0 ** rng.uniform(-3, np.log10(32.0), N), rng.uniform(0, 32, N), np.full(N, 32.0))
+    t = np.where(rng.uniform(0, 1, N) < 0.12, rng.uniform(32.0, 50.0, N) + 1e-9, t)
+
+    def argument(k):        # both sides of the method boundaries x = 1/2, x = a - 1/3, x^a = 1/2; x = a; the far tail
+        near = 1.0 + sign() * 10.0 ** rng.uniform(-16, -1, N)
+        u = pick(t * 10.0 ** rng.uniform(-1, 1, N), np.abs(t - 1.0 / 3.0) * near, 0.5 * near, t * near,
+                 0.5 ** (1.0 / t) * near, rng.uniform(0, 60, N), 10.0 ** rng.uniform(-5, 2.8, N), np.full(N, 0.5))
+        return np.where(outside[:, k], -rng.uniform(0.1, 5.0, N), u)
+    u2, u3 = argument(2), argument(3)
+    # erfcinv(x4) + lowergamma(7/3, a4 x4): x4 in (0, 2), the product through 1/2 and 2
+    x4 = np.where(outside[:, 4], rng.choice([-1.0, 1.0], N) * rng.uniform(2.0, 4.0, N),
+                  pick(rng.uniform(0, 2, N), 10.0 ** rng.uniform(-8, 0, N), rng.uniform(0.2, 1.8, N)))
+    y = np.stack([u0 / par[:, 0], u1 * par[:, 1], u2 / par[:, 2], u3 * par[:, 3], x4], axis=1)
+    return y, par, rng.randn(N, 5), t
 
 
 def bessel_ring_batch(B: int, seed: int = SEED, idx=None):
